@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: voices*samples/sec of the fm-synth voice bank.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one 256-frame block of the fm_voice graph over this rank's voice shard (BASELINE.json
 configs[1]: 65 536 voices per GPU, 48 kHz, f32, synthetic note streams already resident in HBM;
@@ -10,10 +10,16 @@ no torch.distributed environment the script launches itself under torch.distribu
 per GPU, RCCL); the driver's own `python -m torch.distributed.run ... bench.py --gpus N` works too.
 Rank 0 prints ONE JSON line.
 
-The K-step timed region (barrier + synchronize on both sides) is run --repeats times (default 5); `value` is the
-MEDIAN region, every region's time is in the line (`regions_ms`).  After the timed regions rank 0 of a one-GPU run
-also measures the REAL-TIME entry (`realtime`: blocking og_midi_process_block, one launch per 256-frame block, live
-MIDI, p50 / p99 / max wall latency against the 5.333 ms deadline) and the CPU baseline (`cpu_baseline`).
+A plain run times ONE region of exactly K steps (barrier + synchronize on both sides) after the warm-up, which is at
+least W blocks and ~40 ms of work, so that the GPU's clock governor has settled when the clock starts; `ms_per_step` =
+the region / K.  --dump-outputs DIR writes the mix bus of the last timed step as DIR/bus.npy (float32, [frames, channels]);
+the inputs are seeded, so the same arguments give the same bus on every run.
+
+--full adds everything that is not the headline figure: the K-step region run --repeats times (default: ~40 ms of
+timed work, 5..48 regions; `value` is then the MEDIAN region, every region's time is in the detail record), the other
+BASELINE configurations (`configs`; N > 1: `config4` and the `og_cluster` leg), the REAL-TIME entry (`realtime`:
+blocking og_midi_process_block, one launch per 256-frame block, live MIDI, p50 / p99 / max wall latency against the
+5.333 ms deadline) and the CPU baseline (`cpu_baseline`).
 
 `--gpus N --cluster` runs the same workload through the C-ABI cluster (og_cluster_*: ONE process, one engine per GPU,
 one batched ncclReduce per launch batch) instead of one torch.distributed rank per GPU.
@@ -406,7 +412,7 @@ def _realtime_record(graph, block, voices_list, n_blocks, midi_per_block, device
     # the LOADED bank: every voice plays the synthetic score the throughput lines use, plus the live messages
     loaded = []
     # (64 M events = 1 GB on the device, ~6 GB of host memory while the timeline is built, ~5 s of set-up per bank: the
-    #  default `python bench.py` has to finish within minutes)
+    #  default `python bench.py --full` has to finish within minutes)
     max_events = min(64e6, _mem_budget_bytes() / 100.0)
     for V in loaded_voices:
         loaded.append(_rt_bank(graph, V, block, loaded_blocks, 0, midi_per_block, device, deadline_ms, True, max_events))
@@ -855,7 +861,7 @@ def region_stats(times, total_voices, K, block):
     }
 
 
-def cluster_record(args, N, V, K, W, R, graph=None):
+def cluster_record(args, N, V, K, W, R, graph=None, dump_dir=None):
     """The workload through the C-ABI cluster (og_cluster_create over devices 0..N-1, og_cluster_render of the K blocks inside
     the timed region: per-shard host threads, one batched ncclReduce over xGMI): what a Rust / C caller of liboscen_gpu.so
     gets on a multi-GPU node.  Returns the record; `--cluster` prints it as the line, a `--gpus N` run without the flag
@@ -919,6 +925,8 @@ def cluster_record(args, N, V, K, W, R, graph=None):
     red_total_ms, red_n = cl.reduce_time_ms()
     cl.enable_reduce_timing(False)
     assert np.isfinite(mix).all() and np.abs(mix).max() > 0.0, "bus is silent or non-finite"
+    if dump_dir:
+        dump_outputs(dump_dir, np.asarray(mix, dtype=np.float32).reshape(K, block, -1)[-1])
     elapsed, stats = region_stats(times, total_voices, K, block)
     line = {
         "metric": "voices*samples/sec (fm-synth graph, 48 kHz)",
@@ -1123,9 +1131,19 @@ def emit_line_and_exit(line, extra):
     os._exit(0)
 
 
+def dump_outputs(d, bus):
+    """--dump-outputs: what a caller of the timed path received from its last step, the mix bus of the last timed block
+    ([frames, channels] float32), as <d>/bus.npy."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "bus.npy"), np.ascontiguousarray(bus, dtype=np.float32))
+
+
 def run_cluster(args):
     """--cluster: ONE process drives every GPU through the C-ABI cluster."""
-    line = cluster_record(args, args.gpus, args.voices_per_gpu, args.steps, args.warmup, args.repeats if args.repeats > 0 else 5)
+    R = args.repeats if args.repeats > 0 else (5 if args.full else 1)
+    line = cluster_record(args, args.gpus, args.voices_per_gpu, args.steps, args.warmup, R, dump_dir=args.dump_outputs)
     emit(line)
 
 
@@ -1134,9 +1152,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=188)   # 188 x 256 frames = 1 s of audio
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: repeated timed regions, the other BASELINE configurations "
+                         "(N > 1: config4 and the og_cluster leg), the real-time record and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the mix bus of the last timed step to DIR/bus.npy (float32, [frames, channels])")
     ap.add_argument("--repeats", type=int, default=0,
                     help="how many times the K-step timed region is run (value = the median region; every region is in the line).  "
-                         "0 = as many as make ~40 ms of timed work, at least 5 and at most 48: the GPU's clock governor needs tens of "
+                         "0 = one region after a warm-up of ~40 ms of work; with --full, as many as make ~40 ms of timed work, at least 5 "
+                         "and at most 48: the GPU's clock governor needs tens of "
                          "milliseconds of load to settle (measured round 5: forty-eight 0.75 ms regions in a row go 0.76 -> 0.68 ms, "
                          "the cycle count per frame of the kernel is the same throughout -- GRBM_GUI_ACTIVE), so five regions of 20 "
                          "blocks measure the governor, not the kernel")
@@ -1247,16 +1271,25 @@ def main():
         dist.init_process_group(args.backend, rank=rank, world_size=world_size)
 
     V, K, W = args.voices_per_gpu, args.steps, args.warmup
+    W_run = W  # warm-up blocks rendered
     if args.repeats > 0:
         R, repeats_rule = args.repeats, "--repeats %d" % args.repeats
-    else:
+    elif args.full:
         est_region_ms = max(1e-3, K * 0.045 * V / 65536.0)  # ~0.045 ms per 256-frame block of 65 536 fm voices
         R = int(max(5, min(48, -(-40.0 // est_region_ms))))
         repeats_rule = "auto: ~40 ms of timed work (5..48 regions) so that the clock governor has settled by the median region"
+    else:
+        # ONE region of exactly K timed blocks.  The clock governor needs ~40 ms of load to settle (see --repeats): the
+        # warm-up is stretched to that much estimated work, a block count fixed by the arguments, so that the same
+        # arguments render the same blocks on every run.  (The load has to be this bank's own: measured on MI355X, ~40 ms
+        # on a second bank closed right before the warm-up leaves the region at the cold clock.)
+        R = 1
+        W_run = max(W, min(1024, int(-(-40.0 // max(0.01, 0.045 * V / 65536.0)))))
+        repeats_rule = "one region of --steps blocks after %d warm-up blocks (~40 ms of work: the clock governor settles first)" % W_run
     # wall-clock budget of the run, leg by leg (N > 1: the driver's 8-GPU command = headline + config4 + og_cluster; the line
     # carries it so that the run can be seen to fit a timeout before one is hit -- VERDICT r5, item 8)
     t_legs, t_leg0 = {}, time.time()
-    m = timed_bank(args, args.graph, V, K, W, R, rank, local_rank, world_size, dist, args.variant)
+    m = timed_bank(args, args.graph, V, K, W_run, R, rank, local_rank, world_size, dist, args.variant)
     t_legs["headline"] = time.time() - t_leg0
     eng, times, kern_ms, n_launch, n_blocks_timed, multi_gpu = m.eng, m.times, m.kern_ms, m.n_launch, m.n_blocks_timed, m.multi_gpu
     rccl_ranks, timed_blocks, bus, host_bus, midi = m.rccl_ranks, m.timed_blocks, m.bus, m.host_bus, m.midi
@@ -1266,7 +1299,7 @@ def main():
     # the same RCCL reduce, as a sub-record of the line (the driver's command does not pass --voices-per-gpu)
     config4 = None
     V4 = max(64, 262144 // args.test_scale)
-    if world_size > 1 and not args.no_configs and args.graph == "fm_voice" and not args.midi_live and not args.variant and V4 != V:
+    if args.full and world_size > 1 and not args.no_configs and args.graph == "fm_voice" and not args.midi_live and not args.variant and V4 != V:
         K4, W4, R4 = (188, 8, 3) if args.test_scale == 1 else (4, 2, 2)
         t_leg0 = time.time()
         m4 = timed_bank(args, "fm_voice", V4, K4, W4, R4, rank, local_rank, world_size, dist, None)
@@ -1290,6 +1323,8 @@ def main():
         sel = torch.from_numpy(timed_blocks)
         mix = host_bus[timed_blocks] if (midi is not None and args.midi_blocking) else bus[sel.to(bus.device)].float().cpu().numpy()
         assert np.isfinite(mix).all() and np.abs(mix).max() > 0.0, "bus is silent or non-finite"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, mix[-1].reshape(block, -1))
         elapsed, stats = region_stats(times, total_voices, K, block)
         value = total_voices * K * block / elapsed
         line = {
@@ -1364,7 +1399,7 @@ def main():
     # back first -- engine closed, allocator emptied -- and say so through a file; rank 0 waits for every such file before it
     # touches their devices (torchrun gives no "the others are done" signal once the process group is gone).
     release_dir = None
-    cluster_leg = world_size > 1 and not args.no_configs and not args.midi_live and not args.variant
+    cluster_leg = args.full and world_size > 1 and not args.no_configs and not args.midi_live and not args.variant
     if cluster_leg:
         import tempfile
         release_dir = os.path.join(tempfile.gettempdir(), "oscen_bench_release_%d_%s" % (os.getppid(), os.environ.get("MASTER_PORT", "0")))
@@ -1419,12 +1454,12 @@ def main():
                 line["og_cluster"]["ranks_released_devices_first"] = released
             t_legs["og_cluster"] = time.time() - t_leg0
         configs = None
-        if world_size == 1 and not args.no_configs and args.graph == "fm_voice" and not args.midi_live and not args.variant:
+        if args.full and world_size == 1 and not args.no_configs and args.graph == "fm_voice" and not args.midi_live and not args.variant:
             eng.close()
             torch.cuda.synchronize()
             configs = config_records(args, local_rank)
             line["configs_detail"] = configs
-        if world_size == 1 and not args.no_realtime and has_gate and args.graph == "fm_voice":
+        if args.full and world_size == 1 and not args.no_realtime and has_gate and args.graph == "fm_voice":
             torch.cuda.synchronize()
             env = dict(os.environ)
             env["HIP_VISIBLE_DEVICES"] = env.get("HIP_VISIBLE_DEVICES", "").split(",")[local_rank] if env.get("HIP_VISIBLE_DEVICES") else str(local_rank)
@@ -1448,7 +1483,7 @@ def main():
             line["realtime_voices_at_48k"] = line["realtime"]["realtime_voices_at_48k"]
         else:
             line["realtime"] = None
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             # (the oracle folds the plan the same way; a rotated plan of more than a second reads the same in any window)
             line["cpu_baseline"] = cpu_baseline(block, oscen_amd.SYNTH_SEED, K * block, span if span <= 48000 else 47999)
         else:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # driver's command against blocks per launch: is one 20-block launch the best way to render 20 blocks?
 for r in 1 2 3; do for b in 0 10 7 5 4; do
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-realtime --bus-batch $b 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-realtime --bus-batch $b 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

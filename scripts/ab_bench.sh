@@ -9,7 +9,7 @@ for r in $(seq 1 $ROUNDS); do
     if [ -f "$PWD/oscen_amd/_build/liboscen_gpu_$t.env" ]; then set -a; . "$PWD/oscen_amd/_build/liboscen_gpu_$t.env"; set +a; fi
     if [ "$t" = "base" ]; then unset OSCEN_GPU_LIB; else export OSCEN_GPU_LIB=$PWD/oscen_amd/_build/liboscen_gpu_$t.so; fi
     case $t in u[0-9]*) export OGC_UNROLL=${t#u};; esac
-    python bench.py --steps 94 --warmup 4 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 94 --warmup 4 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

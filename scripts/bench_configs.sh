@@ -1,6 +1,6 @@
 #!/bin/bash
 # the BASELINE.json configs on one GPU (values for BASELINE.md / DESIGN.md); run through gpurun
-run() { python bench.py --steps 94 --warmup 4 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --steps 94 --warmup 4 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

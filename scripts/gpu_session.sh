@@ -15,22 +15,22 @@ for p in $PARTS; do
     fullsize)
       timeout 900 python -m pytest tests/test_fullsize_gpu.py -m gpu -x -q -s > $OUT/fullsize.log 2>&1; echo "rc=$?" >> $OUT/fullsize.log ;;
     bench)
-      timeout 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-      timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
-      timeout 300 python bench.py --steps 20 --warmup 5 --sparse-events --no-cpu-baseline > $OUT/bench_driver_sparse.json 2> $OUT/bench_driver_sparse.err
+      timeout 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+      timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+      timeout 300 python bench.py --full --steps 20 --warmup 5 --sparse-events --no-cpu-baseline > $OUT/bench_driver_sparse.json 2> $OUT/bench_driver_sparse.err
       for v in 262144 1048576; do
-        timeout 300 python bench.py --voices-per-gpu $v --no-cpu-baseline > $OUT/bench_fm_$v.json 2> $OUT/bench_fm_$v.err
+        timeout 300 python bench.py --full --voices-per-gpu $v --no-cpu-baseline > $OUT/bench_fm_$v.json 2> $OUT/bench_fm_$v.err
       done
-      timeout 300 python bench.py --graph epiano_voice --voices-per-gpu 262144 --steps 94 --no-cpu-baseline > $OUT/bench_epiano.json 2> $OUT/bench_epiano.err
-      timeout 300 python bench.py --graph sat4x_voice --voices-per-gpu 131072 --steps 94 --no-cpu-baseline > $OUT/bench_sat4x.json 2> $OUT/bench_sat4x.err
-      timeout 300 python bench.py --graph sub_voice --voices-per-gpu 262144 --steps 94 --no-cpu-baseline > $OUT/bench_sub.json 2> $OUT/bench_sub.err
-      timeout 300 python bench.py --midi-live 1000 --no-cpu-baseline > $OUT/bench_midi_live.json 2> $OUT/bench_midi_live.err
+      timeout 300 python bench.py --full --graph epiano_voice --voices-per-gpu 262144 --steps 94 --no-cpu-baseline > $OUT/bench_epiano.json 2> $OUT/bench_epiano.err
+      timeout 300 python bench.py --full --graph sat4x_voice --voices-per-gpu 131072 --steps 94 --no-cpu-baseline > $OUT/bench_sat4x.json 2> $OUT/bench_sat4x.err
+      timeout 300 python bench.py --full --graph sub_voice --voices-per-gpu 262144 --steps 94 --no-cpu-baseline > $OUT/bench_sub.json 2> $OUT/bench_sub.err
+      timeout 300 python bench.py --full --midi-live 1000 --no-cpu-baseline > $OUT/bench_midi_live.json 2> $OUT/bench_midi_live.err
       ;;
     nccl)
       # RCCL refuses two ranks on one GPU: (a) the RCCL leg with a one-rank communicator, (b) the self-launching
       # two-rank path on one device with the reduce over gloo
-      timeout 300 python bench.py --dist-single --steps 20 --warmup 4 --no-cpu-baseline > $OUT/rccl1.json 2> $OUT/rccl1.err; echo "rc=$?" >> $OUT/rccl1.err
-      timeout 300 python bench.py --gpus 2 --single-device --backend gloo --steps 20 --warmup 4 --voices-per-gpu 32768 --no-cpu-baseline > $OUT/gloo2.json 2> $OUT/gloo2.err; echo "rc=$?" >> $OUT/gloo2.err ;;
+      timeout 300 python bench.py --full --dist-single --steps 20 --warmup 4 --no-cpu-baseline > $OUT/rccl1.json 2> $OUT/rccl1.err; echo "rc=$?" >> $OUT/rccl1.err
+      timeout 300 python bench.py --full --gpus 2 --single-device --backend gloo --steps 20 --warmup 4 --voices-per-gpu 32768 --no-cpu-baseline > $OUT/gloo2.json 2> $OUT/gloo2.err; echo "rc=$?" >> $OUT/gloo2.err ;;
     dbg)
       timeout 600 python scripts/dbg_fullsize.py > $OUT/dbg.log 2>&1 ;;
     cluster)

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,8 +84,8 @@ CONTRACT = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.timeout(900)
 def test_default_line_carries_every_baseline_configuration(hostsim_env):
-    d = run_bench(hostsim_env, ["--steps", "4", "--warmup", "2", "--repeats", "2", "--voices-per-gpu", "192", "--no-realtime", "--no-cpu-baseline",
-                                "--test-scale", "2048"])
+    d = run_bench(hostsim_env, ["--full", "--steps", "4", "--warmup", "2", "--repeats", "2", "--voices-per-gpu", "192", "--no-realtime",
+                                "--no-cpu-baseline", "--test-scale", "2048"])
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["dtype"] == "f32" and d["vs_baseline"] is None
@@ -108,6 +109,26 @@ def test_default_line_carries_every_baseline_configuration(hostsim_env):
 
 
 @pytest.mark.timeout(600)
+def test_plain_line_times_the_steps_once_and_dumps_the_last_bus(hostsim_env, tmp_path):
+    """A run without --full: one timed region of exactly --steps blocks, none of the other legs, and --dump-outputs writes the
+    mix bus of the last timed block -- the same bus on a second run with the same arguments, and the same as a --repeats 1 run
+    whose warm-up is the blocks the plain run renders for the clock governor."""
+    buses = []
+    for run, warmup in (("a", []), ("b", []), ("c", ["--warmup", "1024", "--repeats", "1"])):
+        out = tmp_path / run
+        d = run_bench(hostsim_env, ["--steps", "3", "--warmup", "2", "--voices-per-gpu", "64", "--block", "64", "--dump-outputs", str(out)] + warmup)
+        assert d["steps"] == 3 and d["warmup"] == (1024 if warmup else 2) and d["_detail"]["timing"]["repeats"] == 1
+        assert abs(d["value"] - 64 * 3 * 64 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+        assert d["realtime"] is None and d["cpu_baseline"] is None and "configs" not in d
+        assert set(d["wall_s"]) == {"headline", "total_since_start"}, d["wall_s"]
+        assert sorted(os.listdir(out)) == ["bus.npy"]
+        buses.append(np.load(out / "bus.npy"))
+    assert buses[0].dtype == np.float32 and buses[0].shape == (64, 1)
+    assert np.isfinite(buses[0]).all() and np.abs(buses[0]).max() > 0.0
+    assert np.array_equal(buses[0], buses[1]) and np.array_equal(buses[0], buses[2])
+
+
+@pytest.mark.timeout(600)
 def test_variant_line(hostsim_env):
     d = run_bench(hostsim_env, ["--steps", "24", "--warmup", "2", "--repeats", "2", "--voices-per-gpu", "128", "--no-realtime", "--no-cpu-baseline",
                                 "--variant", "survey2"])
@@ -122,7 +143,8 @@ def test_eight_rank_line_carries_config4_and_the_og_cluster_leg(hostsim_env, tmp
     scaled down here) through the same ranks, and the `og_cluster` sub-record -- the product's own multi-GPU leg
     (og_cluster_*, the library's ncclReduce over a stand-in librccl) over all eight devices, asserted to span them."""
     script = tmp_path / "bench_harness.py"
-    argv = ["--gpus", "8", "--steps", "4", "--warmup", "2", "--repeats", "2", "--voices-per-gpu", "64", "--backend", "gloo", "--test-scale", "2048"]
+    argv = ["--full", "--gpus", "8", "--steps", "4", "--warmup", "2", "--repeats", "2", "--voices-per-gpu", "64", "--backend", "gloo",
+            "--test-scale", "2048"]
     script.write_text(HARNESS % {"root": ROOT, "argv": argv, "bench": os.path.join(ROOT, "bench.py")})
     env = dict(hostsim_env)
     env["OG_HOSTSIM_DEVICES"] = "8"
