@@ -421,6 +421,14 @@ struct og_engine {
     uint32_t* d_ev_cursor = nullptr;
     float* d_partials = nullptr;
     float* d_partials2 = nullptr; // group sums of the multi-pass bus reduce
+    // ADSR release reciprocals (OgBlockArgs::rcp_tab): entries 1 .. rcp_n, grown (never per block: at least doubled) when a
+    // launch's longest release needs more; a replaced table stays allocated until og_destroy -- launches already queued may
+    // still read it -- so that growing never waits for the device.  Launches whose release exceeds rcp_cap (OG_RCP_MAX;
+    // experiment knob OSCEN_GPU_RCP_CAP) run the v_rcp_f32 bodies.
+    float* d_rcp = nullptr;
+    uint32_t rcp_n = 0;
+    uint32_t rcp_cap = OG_RCP_MAX;
+    std::vector<float*> rcp_old;
     // Block queue (og_set_bus_batching): up to `bus_batch` consecutive async blocks that nothing separates (no value
     // change, no event push, no taps) are rendered by ONE launch of the voice kernel over their frames back to back --
     // state loaded and stored once, one inter-kernel gap, one bus reduce per tree level -- instead of one launch each.
@@ -688,6 +696,8 @@ struct og_engine {
         (void)hipFree(d_ev_cursor);
         (void)hipFree(d_partials);
         (void)hipFree(d_partials2);
+        (void)hipFree(d_rcp);
+        for (float* p : rcp_old) (void)hipFree(p);
         (void)hipFree(d_stage_bus);
         (void)hipFree(d_bus);
         (void)hipFree(d_taps);
@@ -1225,6 +1235,31 @@ struct og_engine {
         if (bulk || !incremental_update()) full_rebuild();
     }
 
+    // the longest release, in samples, of the outer-rate envelopes under these block-uniform slots
+    uint32_t release_need(const uint32_t* slots) const
+    {
+        uint32_t need = 0;
+        for (int k : cg->release_slots) need = std::max(need, slots[k]);
+        return need;
+    }
+    // make the reciprocal table cover `need` entries (stream-ordered: the fill runs ahead of the launches that read it);
+    // false when `need` is over the cap
+    bool rcp_cover(uint32_t need)
+    {
+        if (need > rcp_cap) return false;
+        if (need <= rcp_n) return true;
+        const uint32_t n = std::min(rcp_cap, std::max(need, 2 * rcp_n));
+        float* t = nullptr;
+        HIPCK(hipMalloc(&t, ((size_t)OG_RCP_PAD + n + 1) * sizeof(float)));
+        const uint32_t words = OG_RCP_PAD + n + 1;
+        hipLaunchKernelGGL(og::rcp_table_fill<0>, dim3((words + 255) / 256), dim3(256), 0, stream, t, n);
+        HIPCK(hipGetLastError());
+        if (d_rcp) rcp_old.push_back(d_rcp);
+        d_rcp = t;
+        rcp_n = n;
+        return true;
+    }
+
     void alloc_bus_buffers(uint32_t batch)
     {
         HIPCK(hipStreamSynchronize(stream));
@@ -1369,6 +1404,10 @@ struct og_engine {
             e.block_starts = starts;
             e.n_blocks = nb;
             for (const auto& up : cg->uprogs) A.slots[up.dst] = up.fn(e);
+        }
+        if (rcp_cover(release_need(A.slots))) {
+            A.rcp_tab = d_rcp;
+            A.rcp_len = rcp_n;
         }
         const bool ramps_on = q_ramps && q_ramp_slot >= 0;
         if (ramps_on) {
@@ -1850,6 +1889,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             // 0.325 ms per block -- a wave-instruction costs the same issue time however many of its
             // lanes are active, so narrowing only multiplies instructions.  Kept as an experiment knob.
             e->blocking_memcpy = ogabi::experiment_knob("OSCEN_GPU_BLOCKING_MEMCPY") != nullptr; // (environment knobs are read HERE, once)
+            if (const char* rc = ogabi::experiment_knob("OSCEN_GPU_RCP_CAP")) e->rcp_cap = std::min<uint32_t>(OG_RCP_MAX, (uint32_t)atoll(rc));
             if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) e->ev_headroom_env = std::max<size_t>(64, (size_t)atoll(hv));
             uint32_t lanes = OG_WAVE;
             if (const char* ev = ogabi::experiment_knob("OSCEN_GPU_LANES")) {
@@ -2000,6 +2040,12 @@ int og_init(og_engine* e, float sample_rate)
         e->phys_of.clear(); // (og_group_voices: a fresh state has no voice order to keep)
         e->logical_of.clear();
         e->frame_now = 0;
+        { // the reciprocal table for the releases of the initial parameters, before the first block
+            std::vector<uint32_t> slots((size_t)std::max(e->cg->n_slots, 1), 0u);
+            const ogc::UEnv ev = e->env();
+            for (const auto& up : e->cg->uprogs) slots[up.dst] = up.fn(ev);
+            e->rcp_cover(e->release_need(slots.data()));
+        }
         e->inited = true;
         return OG_OK;
     });

@@ -1227,7 +1227,8 @@ void emit_adsr(NodeCtx& x)
     });
     int s_ai = x.slot_u([ha](const UEnv& e) { return (uint32_t)(ha(e) <= ADSR_MIN_TIME); });
     int s_ri = x.slot_u([hr](const UEnv& e) { return (uint32_t)(fmaxf(hr(e), 0.0f) <= ADSR_MIN_TIME); });
-    (void)s_rn; (void)s_su; (void)s_ai; (void)s_ri; // eight consecutive slots, see og_nodes.hip.h
+    (void)s_su; (void)s_ai; (void)s_ri; // eight consecutive slots, see og_nodes.hip.h
+    if (x.n.domain != 1) x.cg.out.release_slots.push_back(s_rn); // (the chunk loops' releases: og::rcp_fetch)
     const std::string K = "A, " + std::to_string(s_an);
     const std::string E = x.p + "e";
     // state planes keep the reference's fields; the kernel works on the register form og::Adsr
@@ -4304,6 +4305,14 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
                 if (used_here && group_of(groups, xv.from) != gi) reads.push_back(k);
             }
             for (size_t k : reads) body << "    float xp" << k << "[XCH];\n";
+            // Release reciprocals from a table (four-wave shapes; the sticky release loop below, wide form only, og::rcp_fetch):
+            // one 16-byte load per envelope and four frames instead of v_rcp_f32 + a subtraction per envelope and frame.
+            // OGC_RCP_TAB=0 keeps v_rcp_f32 in that loop (A/B).
+            std::vector<std::string> envs; // "<E>" of this wave's outer-rate envelopes
+            if (K == 4 && !(ogabi::experiment_knob("OGC_RCP_TAB") && atoi(ogabi::experiment_knob("OGC_RCP_TAB")) == 0))
+                for (int k : st)
+                    for (const auto& cexp : cg.sec[k].env_cnts) envs.push_back(cexp.substr(0, cexp.size() - 4)); // "<E>.cnt"
+            for (const auto& E : envs) body << "    float " << E << "_rcp[XCH];\n";
             // Ramp-table rows (ramped inputs: the RAMPS variants; stream inputs: every variant).  `RV(row, slot)` / `ST(row)`
             // read A.ramp_table[row * stride + f] -- a scalar load behind a 64-bit address computation, per input and frame:
             // the launches that read the table took 1.8x the time of the others (SALU 2.9x per block, round 5 counters).  In
@@ -4321,6 +4330,13 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
                 }
             }
             for (int r : rows) body << "    float rv_" << r << "[XCH];\n";
+            for (const auto& E : envs) {
+                const std::string from = "og::adsr_tick<decltype(chk)::release, true>(" + E + ")";
+                const std::string to = "og::adsr_tick_chunk<decltype(chk)::release, decltype(chk)::table>(" + E + ", " + E + "_rcp, j)";
+                const size_t pos = tick_text.find(from);
+                if (pos == std::string::npos) throw std::runtime_error("internal: no tick of " + E + " in its wave");
+                tick_text.replace(pos, from.size(), to);
+            }
             body << "    auto tick = [&](const uint32_t f, const uint32_t ch, const uint32_t j, auto chk) __attribute__((always_inline))"
                  << (last ? (out.voice_channels > 1 ? " -> og::OutN<" + std::to_string(out.voice_channels) + ">" : std::string(" -> float")) : std::string()) << " {\n"
                  << tick_text;
@@ -4405,12 +4421,28 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
                 o << ind << "}\n";
                 return o.str();
             };
+            // The quiet release loop of the four-wave form takes its reciprocals from the table in the wide instantiation
+            // (FD_T != 0; the 8-frame one keeps v_rcp_f32): one 16-byte load per envelope and four frames.  A wide launch whose
+            // releases the table does not cover (rcp_len = 0) sends chunks with a releasing lane to the checked body instead
+            // (`rel_ok` in the quiet test below).  Only where the checked body is the alternative (one_checked).
+            bool tab_ok = false;
             auto quiet = [&](const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string()) {
                 const bool pre = !reads.empty() || !rows.empty();
                 const bool loop = sticky && !stay.empty();
                 const std::string ind = loop ? ind0 + "    " : ind0;
+                const bool tab = tab_ok && loop && !envs.empty() && std::string(chk_flag) == "false" && std::string(rel_flag) == "true";
+                if (tab) {
+                    body << ind0 << "if constexpr (FD_T != 0) { // the first chunk's release reciprocals\n";
+                    for (const auto& E : envs) body << ind0 << "    og::rcp_fetch<XCH>(" << E << "_rcp, A, " << E << ".cnt);\n";
+                    body << ind0 << "}\n";
+                }
                 if (loop) body << ind0 << "for (;;) { // sticky: this variant again while its conditions hold\n";
-                if (std::string(rel_flag) == "true") body << fc_sync(st, ind);
+                if (tab)
+                    for (const auto& E : envs) body << ind << "const uint32_t " << E << "_nx = " << E << ".cnt - XCH; // (at the next chunk's top)\n";
+                if (std::string(rel_flag) == "true") {
+                    if (tab) body << ind << "if constexpr (FD_T == 0) {\n" << fc_sync(st, ind + "    ") << ind << "}\n";
+                    else body << fc_sync(st, ind);
+                }
                 if (pre) {
                     body << row_fetch(ind);
                     body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
@@ -4419,12 +4451,19 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
                     if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
                 }
                 const std::string flag = std::string(chk_flag) + ", " + rel_flag + ", " + (pre ? "true" : "false") + ", " +
-                                         (st_flag ? "true" : "false");
+                                         (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "");
                 body << ind << "#pragma unroll\n"
                      << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
                      << ind << "    const uint32_t f = base + j;\n"
-                     << ind << "    " << call(flag) << "\n"
-                     << ind << "}\n";
+                     << ind << "    " << call(flag) << "\n";
+                // (the next chunk's four reciprocals go into the registers these frames have just read: nothing moves across the
+                //  back edge; a chunk the loop then leaves has loaded them for nothing, inside the table's padding)
+                if (tab) {
+                    body << ind << "    if constexpr (FD_T != 0) {\n";
+                    for (const auto& E : envs) body << ind << "        og::rcp_refill<XCH>(" << E << "_rcp, A, " << E << "_nx, j);\n";
+                    body << ind << "    }\n";
+                }
+                body << ind << "}\n";
                 if (loop) {
                     body << ind << "const uint32_t ch1 = ch + 1u, base1 = base + XCH;\n"
                          << ind << "if (!(ch1 < n_chunks && A.frames - base1 >= (uint32_t)XCH && " << stay_path << (stay == "1" ? "" : " && " + stay)
@@ -4557,9 +4596,11 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
             // any bank size of the bench.)  OGC_SLOWPRIO=-1 turns it off.
             const int slow_prio = ogabi::experiment_knob("OGC_SLOWPRIO") ? atoi(ogabi::experiment_knob("OGC_SLOWPRIO")) : 3;
             const bool one_checked = ev_unroll && !mc.empty() && !force; // events and stage ends share ONE unrolled, checked body
+            tab_ok = one_checked && !envs.empty();
+            const std::string rel_ok = tab_ok ? " && (FD_T == 0 || A.rcp_len != 0u || __all((int)(" + rs_sum(st) + " == 0.0f)))" : std::string();
             if (one_checked)
                 body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH)) && __all((int)(" << mc
-                     << " > (uint32_t)XCH))) { // nothing happens in this chunk: no event, no envelope stage end\n";
+                     << " > (uint32_t)XCH))" << rel_ok << ") { // nothing happens in this chunk: no event, no envelope stage end\n";
             else
                 body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH))" << (force && force[0] == 'e' ? " && A.frames == 0u" : "") << ") {\n";
             auto pick = [&](bool st_flag, const std::string& ind) {

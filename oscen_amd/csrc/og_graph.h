@@ -152,6 +152,7 @@ struct CompiledGraph {
     bool bus_tremolo = false;
     HostFn tremolo_rate, tremolo_depth;
     std::vector<UniformProg> uprogs;
+    std::vector<int> release_slots; // release length in samples (ADSR_R_N) of every outer-rate envelope: sizes the reciprocal table
     int n_slots = 0;
     int n_ramps = 0;
     int n_streams = 0; // rows n_ramps.. of the per-frame table taken by graph-level stream inputs (`<stream_in>_block`;

@@ -47,6 +47,8 @@ using __hip_internal::uint64_t;
 #define OG_MAX_LAUNCH_FRAMES (OG_MAX_BLOCK * OG_MAX_LAUNCH_BLOCKS)
 #define OG_MAX_SLOTS 160
 #define OG_BUS_CHUNK 16
+#define OG_RCP_PAD 16       // zero words in front of entry 0 of OgBlockArgs::rcp_tab: room for the next chunk's prefetch (og::rcp_fetch)
+#define OG_RCP_MAX (1u << 24) // largest table: (float)cnt - j is exact below 2^24 (og::Adsr::fc), so the table and v_rcp agree
 #define OG_LANE_DUMP_WORDS 16 // words per lane of OgBlockArgs::lane_dump (og_create allocates OG_WAVE of them; lane_plane_or_dump)
 // the hand-off of the pipelined shapes: one workgroup barrier per chunk.  -DOG_EXPERIMENT_NOSYNC (scripts/build_variant.py
 // <tag> -- -DOG_EXPERIMENT_NOSYNC; never a product build) removes it to time an upper bound: the results are then WRONG.
@@ -140,6 +142,10 @@ struct OgBlockArgs {
     // and last instruction -- the shader clock the launch ran at UNDER ITS OWN LOAD (og_kernel_clock_ghz)
     unsigned long long* clock_out; // [4]
     uint32_t* lane_dump;       // [OG_WAVE][OG_LANE_DUMP_WORDS] words behind the last lane-state plane: the write target of lanes beyond the last voice
+    // ADSR release reciprocals (og::rcp_fetch): rcp_tab[OG_RCP_PAD + n] = v_rcp_f32((float)n) for n = 1 .. rcp_len.  rcp_len = 0:
+    // some envelope of the launch releases for longer than the table covers, and every release body computes v_rcp_f32 itself
+    const float* rcp_tab;
+    uint32_t rcp_len;
     float* rings[OG_MAX_RINGS];        // delay lines: [capacity][n_voices] each (slot-major, voices contiguous)
     uint32_t ring_cap[OG_MAX_RINGS];   // capacity in samples (a power of two, ring_buffer/mod.rs:35-41)
     uint32_t slots[OG_MAX_SLOTS]; // block-uniform values (f32 or u32 bits)
@@ -165,13 +171,15 @@ __device__ __forceinline__ float uniform_f(const float x)
 // compile-time flags passed to the generated tick lambdas: `value` = envelope stage-end checks on,
 // `release` = envelope release arithmetic on (off in chunks where no lane of the wave is releasing),
 // `pre` = the chunk's hand-off values were read from LDS into registers at the top of the chunk,
-// `steady` = node-specific steady-state conditions hold for the whole chunk (Sect::fast_conds)
-template <bool B, bool R = true, bool P = false, bool S = false>
+// `steady` = node-specific steady-state conditions hold for the whole chunk (Sect::fast_conds),
+// `table` = the envelopes' release reciprocals were read from OgBlockArgs::rcp_tab (rcp_fetch)
+template <bool B, bool R = true, bool P = false, bool S = false, bool T = false>
 struct BoolC {
     static constexpr bool value = B;
     static constexpr bool release = R;
     static constexpr bool pre = P;
     static constexpr bool steady = S;
+    static constexpr bool table = T;
 };
 
 // Frame<N> stream payload (oscen-lib/src/frame.rs): N f32 channels of one sample instant, with the arithmetic the
@@ -293,6 +301,55 @@ __device__ __forceinline__ void row_fetch(float (&dst)[N], const float* __restri
     for (uint32_t j = 0; j < N; ++j) dst[j] = src[j];
 #endif
 }
+// ADSR release reciprocals of a quiet release chunk (og_graph.cpp, the release sticky loop of the wide four-wave form).  In such a
+// chunk no lane has an event and every lane's countdown stays above XCH, so the N reciprocals a lane's release needs are
+// v_rcp_f32((float)(cnt - j)), j = 0 .. N-1, known at the chunk's top: one table read per four frames instead of a
+// transcendental and a subtraction per frame, same bits.  top = min(cnt, rcp_len): a lane that does not release (rs = 0 --
+// Attack, Decay, ADSR_HOLD) reads some finite entry, which its fma multiplies by 0.  Entries top - 4g - 3 .. top - 4g are one
+// 16-byte load (dword aligned).  Lowest entry read: 17 - 15 at a chunk's top, 1 - 15 for the prefetch of a next chunk the
+// loop then leaves (OG_RCP_PAD).
+typedef float og_rcp4 __attribute__((ext_vector_type(4), aligned(4)));
+template <uint32_t N>
+__device__ __forceinline__ void rcp_fetch4(float (&r)[N], const OgBlockArgs& a, const uint32_t cnt, const uint32_t g)
+{
+    const uint32_t top = min(cnt, a.rcp_len);
+    const float* p = a.rcp_tab + top + (int)(OG_RCP_PAD - 3 - 4 * g); // (a constant offset from one address per chunk)
+#ifndef OG_HOSTSIM
+    // read-only for the whole launch (built before it, stream-ordered): the constant address space, as in row_fetch
+    typedef __attribute__((address_space(4))) const og_rcp4 crcp4;
+    const og_rcp4 v = *(const crcp4*)(unsigned long long)p;
+#else
+    const og_rcp4 v = *(const og_rcp4*)p;
+#endif
+    r[4 * g] = v.w;
+    r[4 * g + 1] = v.z;
+    r[4 * g + 2] = v.y;
+    r[4 * g + 3] = v.x;
+}
+// the whole chunk's reciprocals (entry to the loop) ...
+template <uint32_t N>
+__device__ __forceinline__ void rcp_fetch(float (&r)[N], const OgBlockArgs& a, const uint32_t cnt)
+{
+    static_assert(N % 4 == 0 && N <= OG_RCP_PAD, "chunk of whole groups of four, prefetch inside the padding");
+#pragma unroll
+    for (uint32_t g = 0; g < N / 4; ++g) rcp_fetch4(r, a, cnt, g);
+}
+// ... and, after frame j of the unrolled body, the next chunk's group of four into the registers its frames have just used
+// (cnt_next = the countdown at the next chunk's top): the loads are in flight for the rest of the chunk
+template <uint32_t N>
+__device__ __forceinline__ void rcp_refill(float (&r)[N], const OgBlockArgs& a, const uint32_t cnt_next, const uint32_t j)
+{
+    if ((j & 3u) == 3u) rcp_fetch4(r, a, cnt_next, j >> 2);
+}
+// the table's entries (og_engine.cpp builds it on the device, with the voice kernels' compiler flags, so that an entry is the
+// instruction's own bits): 0 in the padding and at n = 0, which no releasing lane reads
+template <int = 0>
+__global__ __launch_bounds__(256) void rcp_table_fill(float* tab, const uint32_t len)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i <= OG_RCP_PAD + len) tab[i] = i <= OG_RCP_PAD ? 0.0f : __builtin_amdgcn_rcpf((float)(i - OG_RCP_PAD));
+}
+
 // ... picked by the frame's position in the chunk where the chunk body is the unrolled one; read directly elsewhere
 template <bool PRE, uint32_t N>
 __device__ __forceinline__ float row_pick(const float (&pre)[N], uint32_t j, const OgBlockArgs& a, int row, uint32_t f)

@@ -234,6 +234,29 @@ OG_DEV float adsr_tick(Adsr& e)
     return lv;
 }
 
+// The same tick with the release reciprocal given: r = v_rcp_f32((float)cnt) read from the table of a quiet release chunk
+// (og_kernel_rt.hip.h, rcp_fetch), the same bits as the arithmetic above.  e.fc is not kept: every other chunk body
+// re-derives it at its top.
+OG_DEV float adsr_tick_r(Adsr& e, const float r)
+{
+#ifdef OG_STRICT
+    return adsr_tick<true, false>(e);
+#else
+    const float cf = fmaf(e.rs, r, e.cf);
+    const float lv = fmaf(e.tgt - e.lv, cf, e.lv);
+    e.cnt -= 1u;
+    e.lv = lv;
+    return lv;
+#endif
+}
+// frame j of a chunk body: the table form where the body read the chunk's reciprocals into `rcp`
+template <bool RELEASE, bool TABLE, uint32_t N>
+OG_DEV float adsr_tick_chunk(Adsr& e, const float (&rcp)[N], const uint32_t j)
+{
+    if constexpr (TABLE) return adsr_tick_r(e, rcp[j]);
+    else return adsr_tick<RELEASE, true>(e);
+}
+
 // complete_stage  adsr.rs:175-204 for an envelope whose countdown hit 0 this frame
 OG_DEV void adsr_complete(Adsr& e, float a_c, float d_c, uint32_t d_n, float& out)
 {
