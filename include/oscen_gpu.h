@@ -381,7 +381,8 @@ int og_read_output_events(og_engine* e, og_out_event* buf, uint32_t cap, uint32_
  * og_k_<hash>_*, og_k2_<hash>_*, ... that rocprofv3 reports), and whether it came from hiprtc */
 uint64_t og_kernel_hash(const og_engine* e);
 int og_kernel_is_jit(const og_engine* e);
-const char* og_kernel_name(const og_engine* e); /* "og_k_<hash>" / "og_k2_<hash>" / "og_k4_<hash>": the launched variant family */
+const char* og_kernel_name(const og_engine* e); /* "og_k_<hash>" / "og_k2_<hash>" / "og_k4_<hash>": the launched variant family
+                                                   (+ "_z": the last launch ran the graph's zero variant, og_k*_<hash>_{00,01}z) */
 uint32_t og_partial_rows(const og_engine* e);   /* partial bus rows one launch writes (one per workgroup) */
 /* og_bus_reduce launches of the last block: 1, or 1 + the levels of the multi-pass tree (> 1024 partial rows) */
 uint32_t og_bus_reduce_passes(const og_engine* e);

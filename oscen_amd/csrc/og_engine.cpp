@@ -178,6 +178,17 @@ OgOccupancyFn og_find_occupancy(uint64_t hash)
         if (e->hash == hash) return e->occupancy;
     return nullptr;
 }
+OgZeroKernelEntry*& og_zero_kernel_registry_head()
+{
+    static OgZeroKernelEntry* head = nullptr;
+    return head;
+}
+OgZeroLaunchFn og_find_zero_kernel(uint64_t hash)
+{
+    for (OgZeroKernelEntry* e = og_zero_kernel_registry_head(); e; e = e->next)
+        if (e->hash == hash) return e->launch;
+    return nullptr;
+}
 
 namespace {
 thread_local std::string g_err;
@@ -389,6 +400,9 @@ struct og_engine {
     HostProf prof;
     std::unique_ptr<ogc::CompiledGraph> cg;
     OgLaunchFn launch = nullptr;
+    OgZeroLaunchFn launch_zero = nullptr; // the zero variant of `launch` (og_graph.cpp, ZeroChain), where the graph has one
+    bool zero_spec = true; // launches may run the graph's zero variant (OSCEN_GPU_ZERO_SPEC=0: never)
+    bool last_zero = false; // the last launch ran the zero variant (og_kernel_name)
     std::unique_ptr<OgJitKernel> jit;
     uint32_t V = 0;
     int device = 0;
@@ -1435,10 +1449,21 @@ struct og_engine {
             }
             A.clock_out = h_clock + 4 * t_used; // (pinned host memory is device-visible: four 8-byte stores per launch)
         }
-        if (launch)
+        // The zero variant (og_graph.cpp, ZeroChain): every block of this launch was queued under these slot values (a setter
+        // launches the queue before it changes one) and no ramp ticks in it, so a zero slot here is +-0 on every frame.
+        bool zero = zero_spec && !ramps_on && !cg->zero_slots.empty();
+        for (int zs : cg->zero_slots) zero = zero && (A.slots[zs] & 0x7fffffffu) == 0u;
+        last_zero = false;
+        if (launch && zero && launch_zero) {
+            launch_zero(A, taps_on, stream);
+            last_zero = true;
+        } else if (launch) {
             launch(A, ramps_on, taps_on, stream);
-        else
+        } else if (zero) {
+            last_zero = jit->launch_zero(A, taps_on, stream);
+        } else {
             jit->launch(A, ramps_on, taps_on, stream);
+        }
         if (timed) {
             HIPCK(hipEventRecord(t_stop[t_used], stream));
             ++t_used;
@@ -1878,6 +1903,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
         e->device = device_id;
         HIPCK(hipSetDevice(device_id));
         e->launch = og_find_kernel(e->cg->hash);
+        if (e->launch && !e->cg->zero_slots.empty()) e->launch_zero = og_find_zero_kernel(e->cg->hash);
         if (!e->launch) e->jit = og_jit_compile(*e->cg); // throws if hiprtc is unavailable or fails
         e->V = n_voices;
         // voices per wave: narrow the wave until every SIMD holds two (og_kernel_rt.hip.h)
@@ -1889,6 +1915,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             // 0.325 ms per block -- a wave-instruction costs the same issue time however many of its
             // lanes are active, so narrowing only multiplies instructions.  Kept as an experiment knob.
             e->blocking_memcpy = ogabi::experiment_knob("OSCEN_GPU_BLOCKING_MEMCPY") != nullptr; // (environment knobs are read HERE, once)
+            if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO_SPEC")) e->zero_spec = atoi(zs) != 0;
             if (const char* rc = ogabi::experiment_knob("OSCEN_GPU_RCP_CAP")) e->rcp_cap = std::min<uint32_t>(OG_RCP_MAX, (uint32_t)atoll(rc));
             if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) e->ev_headroom_env = std::max<size_t>(64, (size_t)atoll(hv));
             uint32_t lanes = OG_WAVE;
@@ -2664,7 +2691,8 @@ const char* og_kernel_name(const og_engine* e)
 {
     static thread_local char buf[64];
     if (!e) return "";
-    snprintf(buf, sizeof buf, "og_k%s_%016llx", e->split == 4 ? (e->wide ? "4w" : "4") : (e->split == 2 ? "2" : ""), (unsigned long long)e->cg->hash);
+    snprintf(buf, sizeof buf, "og_k%s_%016llx%s", e->split == 4 ? (e->wide ? "4w" : "4") : (e->split == 2 ? "2" : ""), (unsigned long long)e->cg->hash,
+             e->last_zero ? "_z" : "");
     return buf;
 }
 int og_event_stats(const og_engine* e, uint64_t* full_rebuilds, uint64_t* incremental_updates, uint64_t* resident_events)

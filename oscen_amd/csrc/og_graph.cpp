@@ -74,6 +74,7 @@ struct Val {
     bool lane = false;            // one value per lane of an LPV > 1 voice (an `[f32; 32]` endpoint)
     bool stream = false;          // a graph-level stream input: voice-uniform, but a signal (resampled across rate domains)
     std::vector<Val> ch;          // a Frame<N> payload (oscen-lib/src/frame.rs): its N channels, each a scalar value; `e` unused
+    bool zspec = false;           // the zero variant's stand-in for `c + 0 * env` (a launch-uniform slot or literal: see ZeroChain)
     bool is_frame() const { return !ch.empty(); }
 };
 
@@ -498,6 +499,12 @@ struct Codegen {
     int N = 1;        // oversampling factor of the `* N` nodes (1 = none)
     int n_cross = 0;  // cross-rate edges emitted so far
     bool any_derive = false;
+    // The zero variant (see ZeroChain): the Gain and AddValue nodes of the chains it folds (null: the general kernel), and
+    // what the general pass learned for finding them -- the slot of every Gain's block-uniform gain, the launch form of
+    // every AddValue's block-uniform value
+    const std::set<int>* zero_nodes = nullptr;
+    std::map<int, int> gain_slot;
+    std::map<int, Val> add_launch;
     // pipeline bookkeeping
     bool split = false;
     int n_stages = 1;
@@ -759,7 +766,7 @@ struct Codegen {
         if (vit == node_outputs.end())
             fail("node '" + node_name + "' has no output '" + port + "' (or it is read before it runs)");
         Val v = vit->second;
-        if (split && cs > stage_of[ni]) { // value crosses a pipeline cut
+        if (split && cs > stage_of[ni] && !v.zspec && v.rate != Rate::Const) { // value crosses a pipeline cut (a zero-variant slot or literal does not)
             XVal* x = nullptr;
             for (auto& xv : xvals)
                 if (xv.var == v.e) x = &xv;
@@ -1316,7 +1323,7 @@ void emit_tpt(NodeCtx& x)
     auto block_const = [](const Val& v) { return v.rate <= Rate::VBlock && v.rate != Rate::UFrame; };
     const std::string tail = x.sf(s_maxc) + ", " + x.sf(s_two_sr) + ", " + x.sf(s_period) + ", " + x.sf(s_nyq) + ", " + cc + ", " +
                              cq + ", " + h + ", " + g + ", " + kk + ");\n";
-    if (nomod && block_const(cutoff) && block_const(q) && x.n.domain != 1) {
+    if (nomod && block_const(cutoff) && !cutoff.zspec && block_const(q) && x.n.domain != 1) {
         // cutoff and q cannot change between events: apply_parameter_updates() finds nothing to do after the
         // first frame of the block, so it runs in derive() (block start and after per-voice value events)
         x.cg.S().derive << "        og::tpt_params_nomod(" << cutoff.e << ", " << q.e << ", " << tail;
@@ -1351,8 +1358,16 @@ void emit_tpt(NodeCtx& x)
         const bool q_uniform = q.rate <= Rate::UBlock || q.rate == Rate::UFrame;
         const std::string iq_expr = "1.0f / og::clampf(" + q_launch + ", 0.1f, 10.0f)";
         const std::string iq = q_launch.empty() ? std::string("0.0f") : x.hoist("inv_q", q_uniform ? "og::uniform_f(" + iq_expr + ")" : iq_expr);
-        x.cg.os() << "        og::tpt_params_nomod_lazy<" << qchk << ", " << (q_launch.empty() ? "false" : "true") << ">(" << cutoff.e << ", " << q.e << ", "
-                  << iq << ", " << li << ", " << lq << ", " << tail;
+        if (cutoff.zspec && !q_launch.empty()) {
+            // the zero variant: cutoff and q are launch constants, so the per-frame test fires on the launch's first frame only
+            // (off the sentinel) and after a per-voice value event (which re-derives the same coefficients from the same
+            // inputs).  Run that update here, in derive(): at the top of the launch and on such an event.
+            x.cg.S().derive << "        if (A.frames != 0u) og::tpt_params_nomod_lazy<" << qchk << ", true>(" << cutoff.e << ", " << q_launch << ", "
+                            << iq << ", " << li << ", " << lq << ", " << tail;
+        } else {
+            x.cg.os() << "        og::tpt_params_nomod_lazy<" << qchk << ", " << (q_launch.empty() ? "false" : "true") << ">(" << cutoff.e << ", " << q.e << ", "
+                      << iq << ", " << li << ", " << lq << ", " << tail;
+        }
     } else if (nomod) {
         x.cg.os() << "        og::tpt_params_nomod(" << cutoff.e << ", " << q.e << ", " << tail;
     } else {
@@ -1544,9 +1559,50 @@ void emit_binary(NodeCtx& x, const char* a, const char* b, const char* op)
     const Val vb = x.in(b);
     x.set_out("output", va.e + op + vb.e);
 }
-void emit_gain(NodeCtx& x) { emit_binary(x, "input", "gain", " * "); }
+// The slot a block-uniform value reads in the kernel variants that read no ramp table (`SF(k)`, or the slot of `RV(row, k)`);
+// -1 for anything else
+int uniform_slot(const Val& v)
+{
+    if (v.is_frame() || v.lane || v.stream || !(v.rate == Rate::UBlock || v.rate == Rate::UFrame)) return -1;
+    int row = 0, slot = -1, used = 0;
+    if (sscanf(v.e.c_str(), "SF(%d)%n", &slot, &used) == 1 && used == (int)v.e.size()) return slot;
+    if (sscanf(v.e.c_str(), "RV(%d, %d)%n", &row, &slot, &used) == 2 && used == (int)v.e.size()) return slot;
+    return -1;
+}
+void emit_gain(NodeCtx& x)
+{
+    if (x.cg.zero_nodes && x.cg.zero_nodes->count(x.n.id)) { // zero variant: `env * (+-0)`, folded into the AddValue behind it
+        (void)x.in("gain");
+        Val z = vconst(0.0f);
+        x.cg.node_outputs["n" + std::to_string(x.n.id) + ".output"] = z;
+        return;
+    }
+    const Val va = x.in("input");
+    const Val vb = x.in("gain");
+    x.cg.gain_slot[x.n.id] = uniform_slot(vb);
+    x.set_out("output", va.e + " * " + vb.e);
+}
 void emit_vca(NodeCtx& x) { emit_binary(x, "input", "control", " * "); }
-void emit_add_value(NodeCtx& x) { emit_binary(x, "input", "value", " + "); }
+void emit_add_value(NodeCtx& x)
+{
+    const bool zero = x.cg.zero_nodes && x.cg.zero_nodes->count(x.n.id);
+    const Val va = zero ? Val() : x.in("input");
+    const Val vb = x.in("value");
+    // the value in the kernels that read no ramp table: a literal or a slot
+    Val c = vb;
+    const int slot = uniform_slot(vb);
+    if (slot >= 0) {
+        c.e = "SF(" + std::to_string(slot) + ")";
+        c.rate = Rate::UBlock;
+    }
+    if (vb.rate == Rate::Const || slot >= 0) x.cg.add_launch[x.n.id] = c;
+    if (zero) { // zero variant: `c + (+-0)` is `c`, read where it is used
+        c.zspec = true;
+        x.cg.node_outputs["n" + std::to_string(x.n.id) + ".output"] = c;
+        return;
+    }
+    x.set_out("output", va.e + " + " + vb.e);
+}
 void emit_mixer(NodeCtx& x) { emit_binary(x, "input_a", "input_b", " + "); }
 void emit_hardclip(NodeCtx& x) { x.set_out("output", "og::hardclip(" + x.in("input").e + ")"); }
 void emit_crossfade(NodeCtx& x)
@@ -3008,7 +3064,40 @@ void check_reference_rules(const GraphDesc& g)
     }
 }
 
-std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
+// ---- the zero variant ---------------------------------------------------------
+// A ZeroChain is `env -> Gain(gain = a block-uniform value g) -> AddValue(value = a block-uniform value c)`, the Gain's
+// output read by nothing else and the AddValue's by TPT cutoffs only (FMVoice: env_filter -> filter_env_gain(filter_env_amount)
+// -> cutoff_mod(+ filter_cutoff) -> filter.cutoff).  An ADSR level is finite, so where g is +-0 for a whole launch the sum is
+// c for every frame: `x * +-0` is +-0 and `c + +-0` is c (for c = -0 the sum may be +0: equal as a value, and a TPT clamps
+// its cutoff to [20, max] before anything reads it).  Any other consumer -- one that takes a host or block-constant path for
+// a uniform input, or cares about the sign of zero -- keeps the graph on its general kernel alone.
+// For such a graph the generator emits the kernel a second time (namespace og_gen_<hash>_z, kernels og_k*_<hash>_{00,01}z)
+// with the Gain and AddValue left out: the consumers read c from its slot, no pipeline channel carries the sum, and a TPT
+// filter fed by it runs its lazy cutoff update once per launch (in derive()) instead of testing its input every frame.  The
+// envelope itself still ticks, ends its stages and takes its gate events exactly as in the general kernel.  The engine
+// launches the zero kernel for a launch that reads no ramp table and whose every zero slot holds +-0 (og_engine.cpp).
+// The kernel hash is that of the general kernel: the zero kernel is derived from the same graph by a fixed rule.
+namespace {
+// occurrences of `name.` as an endpoint in an edge source text
+int count_node_refs(const std::string& text, const std::string& name)
+{
+    int n = 0;
+    for (size_t p = text.find(name); p != std::string::npos; p = text.find(name, p + 1)) {
+        const bool left = p == 0 || !(isalnum((unsigned char)text[p - 1]) || text[p - 1] == '_' || text[p - 1] == '.');
+        const size_t e = p + name.size();
+        if (left && (e == text.size() || !(isalnum((unsigned char)text[e]) || text[e] == '_'))) n += 1;
+    }
+    return n;
+}
+} // namespace
+
+std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::set<int>* zero_nodes, std::string* zero_body);
+
+std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in) { return compile_pass(g_in, nullptr, nullptr); }
+
+// zero_nodes == null: the general kernel (and, where the graph has ZeroChains, the zero variant next to it).  Otherwise the
+// zero variant's pass: stops once the kernel body is formed and returns it in *zero_body.
+std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::set<int>* zero_nodes, std::string* zero_body)
 {
     check_reference_rules(g_in);
     const GraphDesc g = expand(g_in);
@@ -3016,6 +3105,7 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     CompiledGraph& out = *cgp;
     out.name = g.name;
     Codegen cg(g, out);
+    cg.zero_nodes = zero_nodes;
 
     // ---- inputs / outputs ----------------------------------------------------
     for (size_t i = 0; i < g.inputs.size(); ++i) {
@@ -4662,6 +4752,76 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     std::string user_src;
     for (const auto& kv : cg.user_fns) user_src += kv.second;
     const std::string body_s = user_src + body.str();
+    if (zero_nodes) {
+        *zero_body = body_s;
+        return cgp;
+    }
+    // ZeroChains (above): the Gain / AddValue nodes and the slots the engine tests
+    std::set<int> zset;
+    const char* zk = ogabi::experiment_knob("OGC_ZERO_SPEC");
+    for (const NodeInst& d : cg.nodes) {
+        if (zk && atoi(zk) == 0) break;
+        if (!d.live || !d.type || d.type->emit != emit_add_value || d.domain == 1 || !cg.add_launch.count(d.id)) continue;
+        auto single_ref = [&](const NodeInst& n, const char* port, Emitter src_type) -> int {
+            auto it = n.in_edges.find(port);
+            if (it == n.in_edges.end() || it->second.size() != 1) return -1;
+            const NodeInst::Src& sr = it->second[0];
+            if (!sr.policy.empty() || sr.e->t != Expr::Ref || sr.e->port != "output") return -1;
+            auto ni = cg.node_by_name.find(sr.e->node);
+            if (ni == cg.node_by_name.end()) return -1;
+            const NodeInst& m = cg.nodes[ni->second];
+            return (m.live && m.type && m.type->emit == src_type && m.domain == n.domain) ? ni->second : -1;
+        };
+        const int gi = single_ref(d, "input", emit_gain);
+        if (gi < 0) continue;
+        const NodeInst& gn = cg.nodes[gi];
+        auto gs = cg.gain_slot.find(gn.id);
+        if (gs == cg.gain_slot.end() || gs->second < 0 || single_ref(gn, "input", emit_adsr) < 0) continue;
+        if (cg.fb_sources.count("n" + std::to_string(gn.id) + ".output")) continue;
+        int refs = 0;
+        for (const GEdge& e : g.edges) refs += count_node_refs(e.src, gn.decl->name);
+        if (refs != 1) continue; // the Gain feeds something besides this AddValue
+        // ... and the AddValue feeds nothing but TPT cutoffs: the one consumer known to give the general kernel's bits from the
+        // constant (every TPT parameter path clamps the cutoff to [20, max] first, so +0 and -0 are alike; the lazy update is
+        // moved to derive() for it).  Any other consumer keeps the general kernel.
+        bool safe = true;
+        int uses = 0;
+        for (const GEdge& e : g.edges) {
+            if (!count_node_refs(e.src, d.decl->name)) continue;
+            uses += 1;
+            const size_t dot = e.dst.rfind('.');
+            auto ti = dot == std::string::npos ? cg.node_by_name.end() : cg.node_by_name.find(e.dst.substr(0, dot));
+            safe = safe && strip_ws(e.src) == d.decl->name + ".output" && !e.feedback && e.policy.empty() && ti != cg.node_by_name.end() &&
+                   e.dst.substr(dot + 1) == "cutoff";
+            if (!safe) break;
+            const NodeInst& tn = cg.nodes[ti->second];
+            auto ce = tn.in_edges.find("cutoff");
+            safe = tn.live && tn.type && tn.type->emit == emit_tpt && tn.domain == d.domain && ce != tn.in_edges.end() && ce->second.size() == 1;
+        }
+        if (!safe || uses == 0) continue;
+        zset.insert(gn.id);
+        zset.insert(d.id);
+        out.zero_slots.push_back(gs->second);
+    }
+    std::string zbody;
+    if (!zset.empty()) {
+        // the engine fills the slots and the state of both kernels from this pass's layout: a zero pass that does not keep it
+        // (or does not compile) leaves the graph without the variant -- it never costs the graph its general kernel
+        bool same = false;
+        try {
+            const auto z = compile_pass(g_in, &zset, &zbody);
+            same = z->n_slots == out.n_slots && z->state.size() == out.state.size() && z->n_ramps == out.n_ramps &&
+                   z->n_streams == out.n_streams && z->lpv == out.lpv && z->max_pipeline == out.max_pipeline && z->wide4 == out.wide4;
+            for (size_t i = 0; same && i < out.state.size(); ++i) same = z->state[i].name == out.state[i].name;
+        } catch (const std::exception&) {
+            same = false;
+        }
+        if (!same) {
+            zset.clear();
+            zbody.clear();
+            out.zero_slots.clear();
+        }
+    }
     // the wide four-wave form: 16-frame chunks, flag hand-off over rings of two chunks (round 6; round 5: one barrier per chunk).
     // OGC_FLAGS="xch,depth" (experiment): `xch` frames per chunk, rings of `depth` chunks, depth 0 = the barrier
     std::string wide_args = "16, 2";
@@ -4690,19 +4850,36 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
         src << "\n// Schedule (depth first from the sinks; same values, any topological order of a pure dataflow graph): ";
         for (auto& nn : out.schedule_order) src << nn << " ";
     }
-    if (out.lpv > 1) src << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
-    if (cg.ev_capacity != 2) src << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
-    src << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n\n"
+    // (the preamble of a unit: the zero variant's unit has the same one)
+    std::ostringstream pre;
+    if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
+    if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
+    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n\n"
         << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
         << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
         << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"
         << "#define ST(row) A.ramp_table[(size_t)(row) * A.ramp_stride + f]\n"
         << "// the pipelined kernels: the chunk's rows are in rv_<row>[] when the chunk body is the unrolled one (BoolC::pre)\n"
         << "#define RVP(row, slot) (RAMPS ? og::row_pick<decltype(chk)::pre>(rv_##row, j, A, (row), f) : og::slot_f(A, (slot)))\n"
-        << "#define STP(row) og::row_pick<decltype(chk)::pre>(rv_##row, j, A, (row), f)\n\n"
+        << "#define STP(row) og::row_pick<decltype(chk)::pre>(rv_##row, j, A, (row), f)\n\n";
+    const char* undefs = "#undef SF\n#undef SU\n#undef RV\n#undef ST\n#undef RVP\n#undef STP\n\n";
+    src << pre.str()
         << "namespace og_gen_" << hs << " {\n"
         << "constexpr int LPV = " << out.lpv << "; // lanes per voice\n"
-        << body_s << "} // namespace\n\n#undef SF\n#undef SU\n#undef RV\n#undef ST\n#undef RVP\n#undef STP\n\n";
+        << body_s << "} // namespace\n\n" << undefs;
+    // the zero variant's unit (csrc/gen/<graph>_z.hip)
+    const bool zv = !zbody.empty();
+    std::ostringstream zsrc;
+    if (zv) {
+        zsrc << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << g.name << "' -- do not edit.\n"
+             << "// The zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroChain): the same kernel for launches in which slot(s)";
+        for (int zs : out.zero_slots) zsrc << " " << zs;
+        zsrc << " hold +-0\n// and no ramp ticks.  Left out:";
+        for (const NodeInst& n : cg.nodes)
+            if (zset.count(n.id)) zsrc << " " << n.decl->name;
+        zsrc << " (their consumers read the AddValue's value from its slot)." << pre.str() << "namespace og_gen_" << hs
+             << "_z {\nconstexpr int LPV = " << out.lpv << "; // lanes per voice\n" << zbody << "} // namespace\n\n" << undefs;
+    }
     const char* variants[4][3] = {{"00", "false", "false"}, {"10", "true", "false"}, {"01", "false", "true"},
                                   {"11", "true", "true"}};
     // register budget of the ordinary kernel: 4 waves per SIMD = 128 VGPRs.  The 4-lanes-per-voice e-piano form
@@ -4715,9 +4892,19 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     // spill inside the frame loop.
     int waves_eu = (out.lpv > 1 && out.lane_width == 8) ? 3 : 4;
     if (const char* ew = ogabi::experiment_knob("OGC_WAVES_EU")) waves_eu = std::max(1, std::min(8, atoi(ew)));
+    // the zero variant: only next to the kernels that read no ramp table (`_00z`, `_01z`)
+    auto zero_variants = [&](const std::function<void(const char* v, const char* taps)>& f) {
+        if (zv)
+            for (auto& v : variants)
+                if (v[1][0] == 'f') f(v[0], v[2]);
+    };
     for (auto& v : variants)
         src << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v[0]
             << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block<" << v[1] << ", " << v[2] << ">(A); }\n";
+    zero_variants([&](const char* v, const char* taps) {
+        zsrc << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v
+            << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block<false, " << taps << ">(A); }\n";
+    });
     std::vector<std::pair<int, int>> depths; // (tag: what OgBlockArgs::split selects, waves per workgroup)
     if (!cg.groups2.empty()) depths.push_back({2, (int)cg.groups2.size()});
     if (!cg.groups4.empty()) depths.push_back({4, (int)cg.groups4.size()});
@@ -4727,34 +4914,68 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
         const int fd = atoi(en);
         if (fd >= 2 && fd <= 8) narrow_args = ", 8, " + std::to_string(fd);
     }
-    for (auto [K, W] : depths)
+    for (auto [K, W] : depths) {
         for (auto& v : variants)
             src << "extern \"C\" __global__ __launch_bounds__(" << 64 * W << ") void og_k" << K << "_" << hs << "_" << v[0]
                 << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block_p" << K << "<" << v[1] << ", " << v[2] << narrow_args << ">(A); }\n";
-    if (out.wide4)
+        // (the narrow four-wave form holds six workgroups per CU; left to itself the compiler gives the zero kernel 82 VGPRs
+        // where the general one has 80 -- five waves per SIMD.  Held to six: 72 VGPRs, no spill)
+        const std::string zbudget = (K == 4 && narrow_args.empty()) ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
+        zero_variants([&, K = K, W = W](const char* v, const char* taps) {
+            zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * W << ")" << zbudget << " void og_k" << K << "_" << hs << "_" << v
+                << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block_p" << K << "<false, " << taps << narrow_args << ">(A); }\n";
+        });
+    }
+    if (out.wide4) {
         for (auto& v : variants)
             src << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v[0]
                 << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block_p4<" << v[1] << ", " << v[2] << ", " << wide_args << ">(A); }\n";
+        zero_variants([&](const char* v, const char* taps) {
+            zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v
+                << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block_p4<false, " << taps << ", " << wide_args << ">(A); }\n";
+        });
+    }
     src << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
         << "static void og_launch_" << hs << "(const OgBlockArgs& A, bool ramps, bool taps, hipStream_t s)\n{\n"
         << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
-    if (out.wide4)
-        src << "    if (A.split == 4u && A.wide) { // four waves per 64 voices, 16-frame hand-offs\n"
-            << "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" << cg.groups4.size() << " * OG_WAVE);\n"
-            << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k4w_" << hs << "_00, gk, bk, 0, s, A);\n"
+    if (zv)
+        zsrc << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
+             << "static void og_launch_" << hs << "_z(const OgBlockArgs& A, bool taps, hipStream_t s)\n{\n"
+             << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
+    // the zero variant's launch of a shape (`kp`: the kernel name up to the hash), inside its `if (A.split ...) {`
+    auto zero_branch = [&](const std::string& kp, const char* dims, const std::string& head) {
+        if (!zv) return;
+        zsrc << head << "        if (taps) hipLaunchKernelGGL(" << kp << hs << "_01z, " << dims << ", 0, s, A);\n"
+             << "        else hipLaunchKernelGGL(" << kp << hs << "_00z, " << dims << ", 0, s, A);\n" << (head.empty() ? "" : "        return;\n    }\n");
+    };
+    if (out.wide4) {
+        const std::string head = std::string("    if (A.split == 4u && A.wide) { // four waves per 64 voices, 16-frame hand-offs\n") +
+                                 "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" + std::to_string(cg.groups4.size()) + " * OG_WAVE);\n";
+        src << head;
+        zero_branch("og_k4w_", "gk, bk", head);
+        src << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k4w_" << hs << "_00, gk, bk, 0, s, A);\n"
             << "        else if (ramps && !taps) hipLaunchKernelGGL(og_k4w_" << hs << "_10, gk, bk, 0, s, A);\n"
             << "        else if (!ramps && taps) hipLaunchKernelGGL(og_k4w_" << hs << "_01, gk, bk, 0, s, A);\n"
             << "        else hipLaunchKernelGGL(og_k4w_" << hs << "_11, gk, bk, 0, s, A);\n"
             << "        return;\n    }\n";
-    for (auto [K, W] : depths)
-        src << "    if (A.split == " << K << "u) { // " << W << " waves per 64 voices\n"
-            << "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" << W << " * OG_WAVE);\n"
-            << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_00, gk, bk, 0, s, A);\n"
+    }
+    for (auto [K, W] : depths) {
+        const std::string head = "    if (A.split == " + std::to_string(K) + "u) { // " + std::to_string(W) + " waves per 64 voices\n" +
+                                 "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" + std::to_string(W) + " * OG_WAVE);\n";
+        src << head;
+        zero_branch("og_k" + std::to_string(K) + "_", "gk, bk", head);
+        src << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_00, gk, bk, 0, s, A);\n"
             << "        else if (ramps && !taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_10, gk, bk, 0, s, A);\n"
             << "        else if (!ramps && taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_01, gk, bk, 0, s, A);\n"
             << "        else hipLaunchKernelGGL(og_k" << K << "_" << hs << "_11, gk, bk, 0, s, A);\n"
             << "        return;\n    }\n";
-    src << "    if (!ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_00, grid, block, 0, s, A);\n"
+    }
+    if (zv) {
+        zsrc << "    if (taps) hipLaunchKernelGGL(og_k_" << hs << "_01z, grid, block, 0, s, A);\n"
+             << "    else hipLaunchKernelGGL(og_k_" << hs << "_00z, grid, block, 0, s, A);\n}\n"
+             << "static const OgZeroKernelRegistrar og_zreg_" << hs << "(0x" << hs << "ull, &og_launch_" << hs << "_z);\n#endif\n";
+    }
+    src <<"    if (!ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_00, grid, block, 0, s, A);\n"
         << "    else if (ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_10, grid, block, 0, s, A);\n"
         << "    else if (!ramps && taps) hipLaunchKernelGGL(og_k_" << hs << "_01, grid, block, 0, s, A);\n"
         << "    else hipLaunchKernelGGL(og_k_" << hs << "_11, grid, block, 0, s, A);\n}\n"
@@ -4769,6 +4990,7 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
         << "static const OgKernelRegistrar og_reg_" << hs << "(0x" << hs << "ull, \"" << g.name << "\", &og_launch_"
         << hs << ", &og_occ_" << hs << ");\n#endif\n";
     out.source = src.str();
+    out.zero_source = zsrc.str();
     return cgp;
 }
 

@@ -136,6 +136,7 @@ struct RingSpec { // a per-voice delay line in HBM (Delay's RingBuffer, delay/mo
 struct CompiledGraph {
     std::string name;
     std::string source; // complete HIP translation unit for this graph
+    std::string zero_source; // ... and that of its zero variant (og_graph.cpp, ZeroChain; empty: none): csrc/gen/<graph>_z.hip
     uint64_t hash = 0;  // FNV-1a of the kernel body: AOT registry / JIT cache key
     std::vector<InputInfo> inputs;
     std::vector<StateWord> state;      // per-voice words
@@ -147,6 +148,9 @@ struct CompiledGraph {
     int max_pipeline = 1;              // deepest pipeline variant generated: 1, 2 (og_k2_*) or 4 (og_k4_*)
     bool wide4 = false;                // the four-wave pipeline also exists with 16-frame hand-offs (og_k4w_*): fewer barriers, twice
                                        // the LDS rings -- for banks whose workgroups all fit a CU at once
+    // the zero variant (og_graph.cpp, ZeroChain): slots whose values must all be +-0 for a launch to run og_k*_<hash>_{00,01}z
+    // (empty: the graph has no such kernel)
+    std::vector<int> zero_slots;
     int valu_estimate = 0;             // estimated VALU instructions per frame of one wave of the ordinary kernel (node weights)
     // post-mix stage (electric-piano/src/main.rs:88-96): Tremolo on the summed bus -> Frame<2>
     bool bus_tremolo = false;

@@ -51,7 +51,7 @@ std::vector<char> compile_to_code(const ogc::CompiledGraph& cg, const char* arch
         srcs[i] = bodies[i].c_str();
     }
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, cg.source.c_str(), (cg.name + ".hip").c_str(), 3, srcs, names) != HIPRTC_SUCCESS)
+    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source).c_str(), (cg.name + ".hip").c_str(), 3, srcs, names) != HIPRTC_SUCCESS)
         throw std::runtime_error("oscen jit: hiprtcCreateProgram failed");
     std::string archopt = std::string("--offload-arch=") + arch;
     const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-DOG_JIT=1"};
@@ -78,6 +78,8 @@ struct JitImpl : OgJitKernel {
     hipFunction_t fn2[4] = {}; // two-wave pipeline variants (when the graph has them)
     hipFunction_t fn4[4] = {}; // four-wave pipeline variants
     hipFunction_t fn4w[4] = {}; // ... with 16-frame hand-offs (when the graph has them)
+    // the zero variant (og_graph.cpp, ZeroChain) of each shape, [taps]: only where the graph has one
+    hipFunction_t fnz[2] = {}, fn2z[2] = {}, fn4z[2] = {}, fn4wz[2] = {};
     unsigned lpv = 1;
     ~JitImpl() override
     {
@@ -85,10 +87,20 @@ struct JitImpl : OgJitKernel {
     }
     void launch(const OgBlockArgs& args, bool ramps, bool taps, hipStream_t stream) override
     {
+        run(args, (ramps ? 1 : 0) + (taps ? 2 : 0), fn, fn2, fn4, fn4w, stream);
+    }
+    bool launch_zero(const OgBlockArgs& args, bool taps, hipStream_t stream) override
+    {
+        if (!fnz[0]) return OgJitKernel::launch_zero(args, taps, stream);
+        run(args, taps ? 1 : 0, fnz, fn2z, fn4z, fn4wz, stream);
+        return true;
+    }
+    void run(const OgBlockArgs& args, int vi, const hipFunction_t* fn, const hipFunction_t* fn2, const hipFunction_t* fn4,
+             const hipFunction_t* fn4w, hipStream_t stream)
+    {
         OgBlockArgs a = args;
         size_t sz = sizeof a;
         void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        const int vi = (ramps ? 1 : 0) + (taps ? 2 : 0);
         unsigned K = 1;
         if (a.split == 4 && fn4[vi]) K = 4;
         else if (a.split >= 2 && fn2[vi]) K = 2;
@@ -148,6 +160,19 @@ std::unique_ptr<OgJitKernel> og_jit_compile(const ogc::CompiledGraph& cg)
                 if (hipModuleGetFunction(&k->fn4w[i], k->mod, name4w.c_str()) != hipSuccess)
                     throw std::runtime_error("oscen jit: kernel " + name4w + " not found in module");
             }
+        }
+    }
+    if (!cg.zero_slots.empty()) {
+        const char* zvar[2] = {"00z", "01z"};
+        auto get = [&](hipFunction_t* f, const std::string& name) {
+            if (hipModuleGetFunction(f, k->mod, name.c_str()) != hipSuccess)
+                throw std::runtime_error("oscen jit: kernel " + name + " not found in module");
+        };
+        for (int i = 0; i < 2; ++i) {
+            get(&k->fnz[i], std::string("og_k_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 2) get(&k->fn2z[i], std::string("og_k2_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 4) get(&k->fn4z[i], std::string("og_k4_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 4 && cg.wide4) get(&k->fn4wz[i], std::string("og_k4w_") + hs + "_" + zvar[i]);
         }
     }
     return k;

@@ -12,6 +12,13 @@
 struct OgJitKernel {
     virtual ~OgJitKernel() {}
     virtual void launch(const OgBlockArgs& args, bool ramps, bool taps, hipStream_t stream) = 0;
+    // a launch that may run the zero variant (og_graph.cpp, ZeroChain): an implementation without it runs the general kernel.
+    // Returns whether the zero kernel ran.
+    virtual bool launch_zero(const OgBlockArgs& args, bool taps, hipStream_t stream)
+    {
+        launch(args, false, taps, stream);
+        return false;
+    }
     virtual int occupancy(int depth) = 0; // resident workgroups per CU of the depth-1 / 2 / 4 shape (0: no such shape)
 };
 

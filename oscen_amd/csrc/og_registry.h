@@ -3,6 +3,8 @@
 // function under the FNV-1a hash of its kernel body; og_create() compiles the
 // caller's graph description on the host, hashes the body it would generate
 // and looks the kernel up here (falling back to hiprtc for unknown graphs).
+// A graph's zero variant (csrc/gen/<graph>_z.hip, og_graph.cpp ZeroChain)
+// registers its launch function under the same hash in a registry of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +12,8 @@
 #include "og_kernel_rt.hip.h"
 
 typedef void (*OgLaunchFn)(const OgBlockArgs& args, bool ramps, bool taps, hipStream_t stream);
+// the zero variant: launches that read no ramp table
+typedef void (*OgZeroLaunchFn)(const OgBlockArgs& args, bool taps, hipStream_t stream);
 // workgroups of the depth-1 / 2 / 4 shape of the kernel a CU can hold at once (registers, LDS): what the engine's choice of
 // pipeline depth needs to know (hipOccupancyMaxActiveBlocksPerMultiprocessor); 0 = no such shape
 typedef int (*OgOccupancyFn)(int depth);
@@ -36,5 +40,25 @@ struct OgKernelRegistrar {
         entry.occupancy = occ;
         entry.next = og_kernel_registry_head();
         og_kernel_registry_head() = &entry;
+    }
+};
+
+struct OgZeroKernelEntry {
+    uint64_t hash;
+    OgZeroLaunchFn launch;
+    OgZeroKernelEntry* next;
+};
+
+OgZeroKernelEntry*& og_zero_kernel_registry_head();
+OgZeroLaunchFn og_find_zero_kernel(uint64_t hash);
+
+struct OgZeroKernelRegistrar {
+    OgZeroKernelEntry entry;
+    OgZeroKernelRegistrar(uint64_t hash, OgZeroLaunchFn fn)
+    {
+        entry.hash = hash;
+        entry.launch = fn;
+        entry.next = og_zero_kernel_registry_head();
+        og_zero_kernel_registry_head() = &entry;
     }
 };
