@@ -187,6 +187,7 @@ extern "C" {
     pub fn og_kernel_blocks_timed(e: *const og_engine) -> u64;
     pub fn og_kernel_is_jit(e: *const og_engine) -> c_int;
     pub fn og_kernel_name(e: *const og_engine) -> *const c_char;
+    pub fn og_kernel_fold_tier(e: *const og_engine) -> c_int;
     pub fn og_uses_split_kernel(e: *const og_engine) -> c_int;
     pub fn og_lanes_per_voice(e: *const og_engine) -> u32;
     pub fn og_voices_per_wave(e: *const og_engine) -> u32;
@@ -195,6 +196,7 @@ extern "C" {
     pub fn og_state_words_per_voice(e: *const og_engine) -> u32;
     pub fn og_state_words_written_per_voice(e: *const og_engine) -> u32;
     pub fn og_graph_kernel_source(g: *const og_graph_desc, buf: *mut c_char, cap: usize) -> i64;
+    pub fn og_graph_variant_source(g: *const og_graph_desc, tier: c_int, buf: *mut c_char, cap: usize) -> i64;
     pub fn og_graph_jit_check(g: *const og_graph_desc, arch: *const c_char) -> i64;
     pub fn og_midi_dropped(m: *const og_midi) -> u64;
     pub fn og_midi_pop_output(m: *mut og_midi, voice: *mut u32, frame: *mut u32, frequency: *mut c_float,

@@ -201,6 +201,9 @@ void og_graph_free(og_graph_desc* g);
 /* The HIP source of the fused voice kernel this description lowers to (for
  * inspection / ahead-of-time builds).  Returns the length; copies at most cap-1 bytes. */
 int64_t og_graph_kernel_source(const og_graph_desc* g, char* buf, size_t cap);
+/* ... and that of the specialised units generated next to it (see og_kernel_fold_tier): tier 0 is the source above, 1 the zero
+ * variant's unit, 2 the deeper zero variant's.  A graph without such a unit has length 0. */
+int64_t og_graph_variant_source(const og_graph_desc* g, int tier, char* buf, size_t cap);
 /* Compile that source with hiprtc for `arch` (e.g. "gfx950") without touching a
  * device -- the path og_create() takes for graphs that were not compiled ahead
  * of time.  Returns the code-object size in bytes, or a negative OG_E_* code. */
@@ -382,7 +385,14 @@ int og_read_output_events(og_engine* e, og_out_event* buf, uint32_t cap, uint32_
 uint64_t og_kernel_hash(const og_engine* e);
 int og_kernel_is_jit(const og_engine* e);
 const char* og_kernel_name(const og_engine* e); /* "og_k_<hash>" / "og_k2_<hash>" / "og_k4_<hash>": the launched variant family
-                                                   (+ "_z": the last launch ran the graph's zero variant, og_k*_<hash>_{00,01}z) */
+                                                   (+ "_z": the last launch ran one of the graph's zero variants, og_k*_<hash>_{00,01}z
+                                                   or og_k*_<hash>_{00,01}z2) */
+/* which kernel the last launch ran: 0 the general one, 1 the zero variant (`_z`: a modulation amount of +-0 folded out), 2 the
+ * deeper zero variant (`_z2`: also operator feedbacks and a crossfade mix of +-0 folded out, operator levels finite).  The
+ * folded kernels give the general kernel's bits, with one exclusion: a state loaded with og_load_state() whose FmOperator
+ * prev_output words are not finite (the general kernel turns NaN * 0 into NaN; the `_z2` kernels, like every operator with
+ * an unconnected feedback, do not multiply at all). */
+int og_kernel_fold_tier(const og_engine* e);
 uint32_t og_partial_rows(const og_engine* e);   /* partial bus rows one launch writes (one per workgroup) */
 /* og_bus_reduce launches of the last block: 1, or 1 + the levels of the multi-pass tree (> 1024 partial rows) */
 uint32_t og_bus_reduce_passes(const og_engine* e);

@@ -183,10 +183,10 @@ OgZeroKernelEntry*& og_zero_kernel_registry_head()
     static OgZeroKernelEntry* head = nullptr;
     return head;
 }
-OgZeroLaunchFn og_find_zero_kernel(uint64_t hash)
+OgZeroLaunchFn og_find_zero_kernel(uint64_t hash, int tier)
 {
     for (OgZeroKernelEntry* e = og_zero_kernel_registry_head(); e; e = e->next)
-        if (e->hash == hash) return e->launch;
+        if (e->hash == hash && e->tier == tier) return e->launch;
     return nullptr;
 }
 
@@ -402,7 +402,12 @@ struct og_engine {
     OgLaunchFn launch = nullptr;
     OgZeroLaunchFn launch_zero = nullptr; // the zero variant of `launch` (og_graph.cpp, ZeroChain), where the graph has one
     bool zero_spec = true; // launches may run the graph's zero variant (OSCEN_GPU_ZERO_SPEC=0: never)
-    bool last_zero = false; // the last launch ran the zero variant (og_kernel_name)
+    bool last_zero = false; // the last launch ran a zero variant (og_kernel_name)
+    // the deeper zero variant (og_graph.cpp, ZeroFolds): tier 2 of the registry
+    OgZeroLaunchFn launch_zero2 = nullptr;
+    bool zero2_spec = true; // launches may run it (OSCEN_GPU_ZERO2_SPEC=0, or OSCEN_GPU_ZERO_SPEC=0: never)
+    bool guards_held = true; // every launch so far had finite values in cg->finite_slots: no operator state can hold inf / NaN
+    int last_tier = 0;       // what the last launch ran: 0 general, 1 zero variant, 2 deeper zero variant (og_kernel_fold_tier)
     std::unique_ptr<OgJitKernel> jit;
     uint32_t V = 0;
     int device = 0;
@@ -1453,8 +1458,18 @@ struct og_engine {
         // launches the queue before it changes one) and no ramp ticks in it, so a zero slot here is +-0 on every frame.
         bool zero = zero_spec && !ramps_on && !cg->zero_slots.empty();
         for (int zs : cg->zero_slots) zero = zero && (A.slots[zs] & 0x7fffffffu) == 0u;
+        // The deeper zero variant (ZeroFolds) also needs finite operator levels -- in this launch and in every one before it:
+        // an inf or NaN an earlier launch left in an operator's prev_output stays there under the general kernel (NaN * 0).
+        for (int fs : cg->finite_slots) guards_held = guards_held && (A.slots[fs] & 0x7f800000u) != 0x7f800000u;
+        bool zero2 = zero_spec && zero2_spec && guards_held && !ramps_on && !cg->zero2_slots.empty();
+        for (int zs : cg->zero2_slots) zero2 = zero2 && (A.slots[zs] & 0x7fffffffu) == 0u;
         last_zero = false;
-        if (launch && zero && launch_zero) {
+        last_tier = 0;
+        if (zero2 && (launch ? launch_zero2 != nullptr : jit->launch_zero2(A, taps_on, stream))) {
+            if (launch) launch_zero2(A, taps_on, stream);
+            last_zero = true;
+            last_tier = 2;
+        } else if (launch && zero && launch_zero) {
             launch_zero(A, taps_on, stream);
             last_zero = true;
         } else if (launch) {
@@ -1464,6 +1479,7 @@ struct og_engine {
         } else {
             jit->launch(A, ramps_on, taps_on, stream);
         }
+        if (last_zero && last_tier == 0) last_tier = 1;
         if (timed) {
             HIPCK(hipEventRecord(t_stop[t_used], stream));
             ++t_used;
@@ -1877,6 +1893,24 @@ int64_t og_graph_kernel_source(const og_graph_desc* g, char* buf, size_t cap)
     return rc == OG_OK ? len : rc;
 }
 
+int64_t og_graph_variant_source(const og_graph_desc* g, int tier, char* buf, size_t cap)
+{
+    if (!g || tier < 0 || tier > 2) return set_err(OG_E_INVALID, "null graph or no such tier");
+    int64_t len = -1;
+    int rc = guard([&] {
+        auto cg = ogc::compile(g->g);
+        const std::string& src = tier == 2 ? cg->zero2_source : (tier == 1 ? cg->zero_source : cg->source);
+        len = (int64_t)src.size();
+        if (buf && cap) {
+            size_t n = std::min(cap - 1, src.size());
+            memcpy(buf, src.data(), n);
+            buf[n] = 0;
+        }
+        return OG_OK;
+    });
+    return rc == OG_OK ? len : rc;
+}
+
 int64_t og_graph_jit_check(const og_graph_desc* g, const char* arch)
 {
     if (!g || !arch) return set_err(OG_E_INVALID, "null argument");
@@ -1904,6 +1938,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
         HIPCK(hipSetDevice(device_id));
         e->launch = og_find_kernel(e->cg->hash);
         if (e->launch && !e->cg->zero_slots.empty()) e->launch_zero = og_find_zero_kernel(e->cg->hash);
+        if (e->launch && !e->cg->zero2_slots.empty()) e->launch_zero2 = og_find_zero_kernel(e->cg->hash, 2);
         if (!e->launch) e->jit = og_jit_compile(*e->cg); // throws if hiprtc is unavailable or fails
         e->V = n_voices;
         // voices per wave: narrow the wave until every SIMD holds two (og_kernel_rt.hip.h)
@@ -1916,6 +1951,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             // lanes are active, so narrowing only multiplies instructions.  Kept as an experiment knob.
             e->blocking_memcpy = ogabi::experiment_knob("OSCEN_GPU_BLOCKING_MEMCPY") != nullptr; // (environment knobs are read HERE, once)
             if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO_SPEC")) e->zero_spec = atoi(zs) != 0;
+            if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO2_SPEC")) e->zero2_spec = atoi(zs) != 0;
             if (const char* rc = ogabi::experiment_knob("OSCEN_GPU_RCP_CAP")) e->rcp_cap = std::min<uint32_t>(OG_RCP_MAX, (uint32_t)atoll(rc));
             if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) e->ev_headroom_env = std::max<size_t>(64, (size_t)atoll(hv));
             uint32_t lanes = OG_WAVE;
@@ -2695,6 +2731,7 @@ const char* og_kernel_name(const og_engine* e)
              e->last_zero ? "_z" : "");
     return buf;
 }
+int og_kernel_fold_tier(const og_engine* e) { return e ? e->last_tier : 0; }
 int og_event_stats(const og_engine* e, uint64_t* full_rebuilds, uint64_t* incremental_updates, uint64_t* resident_events)
 {
     if (!e) return set_err(OG_E_INVALID, "null engine");

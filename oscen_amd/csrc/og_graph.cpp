@@ -505,6 +505,10 @@ struct Codegen {
     const std::set<int>* zero_nodes = nullptr;
     std::map<int, int> gain_slot;
     std::map<int, Val> add_launch;
+    // The deeper zero variant (see ZeroFolds): its pass has the FmOperator, Crossfade and Mixer nodes it folds in zero_nodes as
+    // well.  What the general pass learned for finding them: the slot of every FmOperator's block-uniform feedback and level
+    // (-1: neither a slot nor, for the level, a finite literal; -2: a finite literal level) and of every Crossfade's mix
+    std::map<int, int> fm_fb_slot, fm_level_slot, xfade_mix_slot;
     // pipeline bookkeeping
     bool split = false;
     int n_stages = 1;
@@ -1261,6 +1265,7 @@ void emit_adsr(NodeCtx& x)
         x.cg.pending_post.push_back({E + ".cnt", "            " + fix});
 }
 
+int uniform_slot(const Val& v);
 void emit_fm_operator(NodeCtx& x)
 {
     Val bf = x.in("base_freq"), ratio = x.in("ratio"), pm = x.in("phase_mod"), fb = x.in("feedback"),
@@ -1278,7 +1283,11 @@ void emit_fm_operator(NodeCtx& x)
         x.cg.os() << "        const float " << inc << " = " << inc_expr << ";\n";
     }
     // unconnected feedback (0.0) contributes prev*0 + pm = pm for every finite prev: drop the two ops
-    const bool no_fb = fb.rate == Rate::Const && !x.connected("feedback") && x.def("feedback") == 0.0f;
+    // (the deeper zero variant, ZeroFolds rule 1: a feedback slot that holds +-0 for the whole launch is the same case)
+    const bool fold = x.cg.zero_nodes && x.cg.zero_nodes->count(x.n.id);
+    x.cg.fm_fb_slot[x.n.id] = x.connected("feedback") ? uniform_slot(fb) : -1;
+    x.cg.fm_level_slot[x.n.id] = x.connected("level") ? uniform_slot(lvl) : (std::isfinite(x.def("level")) ? -2 : -1);
+    const bool no_fb = fold || (fb.rate == Rate::Const && !x.connected("feedback") && x.def("feedback") == 0.0f);
     x.set_out("output", std::string(no_fb ? "og::fm_operator_tick_nofb(" : "og::fm_operator_tick(") + phase + ", " + prev +
                             ", " + inc + ", " + pm.e + ", " + (no_fb ? "" : fb.e + ", ") + env.e + ", " + lvl.e + ")");
 }
@@ -1603,11 +1612,35 @@ void emit_add_value(NodeCtx& x)
     }
     x.set_out("output", va.e + " + " + vb.e);
 }
-void emit_mixer(NodeCtx& x) { emit_binary(x, "input_a", "input_b", " + "); }
+void emit_crossfade(NodeCtx& x);
+void emit_mixer(NodeCtx& x)
+{
+    if (x.cg.zero_nodes && x.cg.zero_nodes->count(x.n.id)) {
+        // the deeper zero variant (ZeroFolds rule 3): one input is a folded Crossfade's dropped output_b, +-0 on every frame;
+        // the other one passes through
+        auto dropped = [&](const char* port) {
+            auto it = x.n.in_edges.find(port);
+            if (it == x.n.in_edges.end() || it->second.size() != 1 || it->second[0].e->t != Expr::Ref || it->second[0].e->port != "output_b") return false;
+            auto ni = x.cg.node_by_name.find(it->second[0].e->node);
+            return ni != x.cg.node_by_name.end() && x.cg.zero_nodes->count(x.cg.nodes[ni->second].id) && x.cg.nodes[ni->second].type->emit == emit_crossfade;
+        };
+        x.set_out("output", x.in(dropped("input_b") ? "input_a" : "input_b").e);
+        return;
+    }
+    emit_binary(x, "input_a", "input_b", " + ");
+}
 void emit_hardclip(NodeCtx& x) { x.set_out("output", "og::hardclip(" + x.in("input").e + ")"); }
 void emit_crossfade(NodeCtx& x)
 {
     Val in = x.in("input"), mix = x.in("mix");
+    x.cg.xfade_mix_slot[x.n.id] = x.connected("mix") ? uniform_slot(mix) : -1;
+    if (x.cg.zero_nodes && x.cg.zero_nodes->count(x.n.id)) {
+        // the deeper zero variant (ZeroFolds rule 2): mix is +-0 for the whole launch, so output_a is the input and output_b,
+        // +-0, is dropped (a phase_mod that reads it directly adds the literal)
+        x.set_out("output_a", in.e);
+        x.cg.node_outputs["n" + std::to_string(x.n.id) + ".output_b"] = vconst(0.0f);
+        return;
+    }
     std::string m = x.p + "mix";
     x.cg.os() << "        const float " << m << " = og::clamp01(" << mix.e << ");\n";
     x.set_out("output_a", in.e + " * (1.0f - " + m + ")");
@@ -3077,6 +3110,32 @@ void check_reference_rules(const GraphDesc& g)
 // envelope itself still ticks, ends its stages and takes its gate events exactly as in the general kernel.  The engine
 // launches the zero kernel for a launch that reads no ramp table and whose every zero slot holds +-0 (og_engine.cpp).
 // The kernel hash is that of the general kernel: the zero kernel is derived from the same graph by a fixed rule.
+//
+// ---- the deeper zero variant ----------------------------------------------------
+// ZeroFolds: three more things a patch pays for on every frame although a slot that holds +-0 for the whole launch makes them
+// the identity.  They are found by structure (FMVoice at its defaults -- op3_feedback, op2_feedback, route = 0 -- has all of
+// them).  Every fold rests on `phase >= +0`: an FmOperator's phase is fract_phase()'s value in [0, 1), so `phase + t` gives
+// the same bits for t = +0 and t = -0, and a fold that can only turn a -0 into a +0 (or back) in something that is ADDED TO A
+// PHASE changes nothing.  And on finite operator outputs: sin and an ADSR level are bounded, so an operator's output is finite
+// while its level is; the levels the folds lean on are literals or slots the engine tests for the launch (finite_slots).
+//  1. FmOperator feedback.  `feedback` is a block-uniform slot holding +-0: fma(prev_output, +-0, phase_mod) is +-0 +
+//     phase_mod, i.e. phase_mod by value for a finite prev_output (the operator's own output: its envelope must be an ADSR or
+//     a finite literal, its level a finite literal or a tested slot, its phase modulation finite by the same rules).  The
+//     sum is only added to the phase, so the sign of a zero cannot reach the sine: og::fm_operator_tick_nofb, which op1 of
+//     FMVoice runs in the general kernel already.  prev_output is still stored.
+//  2. Crossfade.  `mix` is a block-uniform slot holding +-0: clamp01(+-0) is +-0, 1 - +-0 is 1.0f, and x * 1.0f is x BIT FOR
+//     BIT -- for denormal x only because the kernels do not flush f32 denormals (tests/test_zero2_variant_cpu.py checks the
+//     compiled kernels' mode; the host simulator does not flush either).  output_b = x * +-0 is +-0 for a finite x: the input
+//     must be such an operator's output.  Each output may feed only FmOperator.phase_mod inputs and Mixer inputs of rule 3,
+//     as plain same-rate edges without fan-in, policy or feedback.  output_a becomes the input; output_b is dropped (a
+//     phase_mod that read it directly would add the literal 0 to its phase).
+//  3. Mixer.  One input is a dropped output_b and the output feeds only FmOperator.phase_mod inputs: y + +-0 is y by value (only
+//     y = -0 can come out as +0), and the only readers add it to a phase.  The other input passes through.
+// A candidate that fails its rule keeps its general code; rules 2 and 3 depend on each other and on rule 1 (a fed-back operator
+// is finite only if its feedback is folded), so the candidates are thinned out until all that remain pass.  The unit
+// (namespace og_gen_<hash>_z2, kernels og_k*_<hash>_{00,01}z2, csrc/gen/<graph>_z2.hip) also has the ZeroChain folds.  The
+// engine runs it for a launch that ticks no ramp, with every slot of zero2_slots +-0 and every slot of finite_slots finite.
+// NOT covered: a state loaded from outside with a non-finite prev_output (the general kernel would turn NaN * 0 into NaN).
 namespace {
 // occurrences of `name.` as an endpoint in an edge source text
 int count_node_refs(const std::string& text, const std::string& name)
@@ -4822,6 +4881,156 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             out.zero_slots.clear();
         }
     }
+    // ZeroFolds (above): the FmOperator / Crossfade / Mixer nodes of the deeper zero variant, the slots the engine tests
+    std::set<int> z2set;
+    std::string z2body;
+    {
+        const char* z2k = ogabi::experiment_knob("OGC_ZERO2_SPEC");
+        std::set<int> fb_ops, xfades, mixers; // candidates (node indices), thinned out until every one of them passes its rule
+        auto usable = [&](const NodeInst& n, Emitter type) { return n.live && n.type && n.type->emit == type && n.domain != 1; };
+        for (const NodeInst& d : cg.nodes) {
+            if (z2k && atoi(z2k) == 0) break;
+            auto slot_of = [&](const std::map<int, int>& m) {
+                auto it = m.find(d.id);
+                return it == m.end() ? -1 : it->second;
+            };
+            if (usable(d, emit_fm_operator) && slot_of(cg.fm_fb_slot) >= 0) fb_ops.insert(cg.node_by_name.at(d.decl->name));
+            if (usable(d, emit_crossfade) && slot_of(cg.xfade_mix_slot) >= 0) xfades.insert(cg.node_by_name.at(d.decl->name));
+            if (usable(d, emit_mixer)) mixers.insert(cg.node_by_name.at(d.decl->name));
+        }
+        // the one plain `node.port` source of an input: (node index, port); (-1, "") for anything else -- an unconnected input,
+        // an expression, a fan-in, a policy edge
+        auto src_ref = [&](const NodeInst& n, const std::string& port) -> std::pair<int, std::string> {
+            auto it = n.in_edges.find(port);
+            if (it == n.in_edges.end() || it->second.size() != 1) return {-1, ""};
+            const NodeInst::Src& sr = it->second[0];
+            if (!sr.policy.empty() || sr.e->t != Expr::Ref || sr.e->port.empty()) return {-1, ""};
+            auto ni = cg.node_by_name.find(sr.e->node);
+            if (ni == cg.node_by_name.end() || cg.nodes[ni->second].domain != n.domain) return {-1, ""};
+            return {ni->second, sr.e->port};
+        };
+        auto dropped_in = [&](const NodeInst& m, const char* port) { // a Mixer input that reads a folded Crossfade's output_b
+            const auto r = src_ref(m, port);
+            return r.first >= 0 && r.second == "output_b" && xfades.count(r.first) > 0;
+        };
+        // An operator whose output is finite on every frame, given finite levels: sin and an ADSR level are bounded, the level is
+        // a finite literal or a slot the engine tests (`guards`), and nothing non-finite can reach the sine -- the feedback term
+        // is absent or folded, the phase modulation comes from such operators through folded nodes only.
+        std::function<bool(int, int, std::set<int>*)> finite_op;
+        std::function<bool(int, const std::string&, int, std::set<int>*)> finite_src = [&](int ni, const std::string& port, int depth, std::set<int>* guards) {
+            const NodeInst& n = cg.nodes[ni];
+            if (depth > 16 || !n.live || !n.type) return false;
+            if (n.type->emit == emit_fm_operator) return port == "output" && finite_op(ni, depth + 1, guards);
+            if (n.type->emit == emit_crossfade && xfades.count(ni)) { // output_a: the input; output_b: +-0
+                const auto r = src_ref(n, "input");
+                return port == "output_b" || (port == "output_a" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards));
+            }
+            if (n.type->emit == emit_mixer && mixers.count(ni)) {
+                const auto r = src_ref(n, dropped_in(n, "input_b") ? "input_a" : "input_b");
+                return port == "output" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards);
+            }
+            return false;
+        };
+        finite_op = [&](int ni, int depth, std::set<int>* guards) {
+            const NodeInst& n = cg.nodes[ni];
+            if (!usable(n, emit_fm_operator)) return false;
+            auto def_of = [&](const char* port) {
+                for (const auto& ps : n.type->inputs)
+                    if (!strcmp(ps.name, port)) return (ps.arg >= 0 && (size_t)ps.arg < n.decl->args.size()) ? n.decl->args[ps.arg] : ps.def;
+                return NAN;
+            };
+            if (n.in_edges.count("envelope")) {
+                const auto r = src_ref(n, "envelope");
+                if (r.first < 0 || r.second != "output" || !usable(cg.nodes[r.first], emit_adsr)) return false;
+            } else if (!std::isfinite(def_of("envelope"))) {
+                return false;
+            }
+            const int ls = cg.fm_level_slot.count(n.id) ? cg.fm_level_slot[n.id] : -1;
+            if (ls == -1) return false;
+            if (ls >= 0 && guards) guards->insert(ls);
+            if (n.in_edges.count("feedback") ? !fb_ops.count(ni) : def_of("feedback") != 0.0f) return false;
+            if (!n.in_edges.count("phase_mod")) return (bool)std::isfinite(def_of("phase_mod"));
+            const auto r = src_ref(n, "phase_mod");
+            return r.first >= 0 && finite_src(r.first, r.second, depth, guards);
+        };
+        // every edge that reads `port` of node n is a plain, same-rate edge into an FmOperator's phase_mod or -- where a Mixer may
+        // follow -- into an input of a Mixer that is still a candidate; no fan-in at the consumer, no feedback, no policy
+        auto feeds_only = [&](const NodeInst& n, bool mixer_ok) {
+            for (const GEdge& e : g.edges) {
+                if (!count_node_refs(e.src, n.decl->name)) continue;
+                const std::string sp = strip_ws(e.src);
+                const size_t sdot = sp.rfind('.'), dot = e.dst.rfind('.');
+                if (sdot == std::string::npos || sp.substr(0, sdot) != n.decl->name || dot == std::string::npos || e.feedback || !e.policy.empty())
+                    return false;
+                if (cg.fb_sources.count("n" + std::to_string(n.id) + "." + sp.substr(sdot + 1))) return false;
+                auto ti = cg.node_by_name.find(e.dst.substr(0, dot));
+                if (ti == cg.node_by_name.end()) return false;
+                const NodeInst& t = cg.nodes[ti->second];
+                const std::string tp = e.dst.substr(dot + 1);
+                auto te = t.in_edges.find(tp);
+                if (!t.live || t.domain != n.domain || te == t.in_edges.end() || te->second.size() != 1) return false;
+                const bool to_op = usable(t, emit_fm_operator) && tp == "phase_mod";
+                const bool to_mixer = mixer_ok && mixers.count(ti->second) && (tp == "input_a" || tp == "input_b");
+                if (!to_op && !to_mixer) return false;
+            }
+            return true;
+        };
+        for (bool changed = true; changed;) {
+            changed = false;
+            auto thin = [&](std::set<int>& set, const std::function<bool(int)>& ok) {
+                for (auto it = set.begin(); it != set.end();)
+                    if (!ok(*it)) {
+                        it = set.erase(it);
+                        changed = true;
+                    } else {
+                        ++it;
+                    }
+            };
+            thin(fb_ops, [&](int ni) { return finite_op(ni, 0, nullptr); });
+            thin(xfades, [&](int ni) {
+                const auto r = src_ref(cg.nodes[ni], "input");
+                return r.first >= 0 && finite_src(r.first, r.second, 0, nullptr) && feeds_only(cg.nodes[ni], true);
+            });
+            thin(mixers, [&](int ni) {
+                const NodeInst& m = cg.nodes[ni];
+                return (dropped_in(m, "input_a") || dropped_in(m, "input_b")) && feeds_only(m, false);
+            });
+        }
+        std::set<int> guards, zeros(out.zero_slots.begin(), out.zero_slots.end());
+        for (int ni : fb_ops) {
+            (void)finite_op(ni, 0, &guards);
+            zeros.insert(cg.fm_fb_slot[cg.nodes[ni].id]);
+            z2set.insert(cg.nodes[ni].id);
+        }
+        for (int ni : xfades) {
+            const auto r = src_ref(cg.nodes[ni], "input");
+            (void)finite_src(r.first, r.second, 0, &guards);
+            zeros.insert(cg.xfade_mix_slot[cg.nodes[ni].id]);
+            z2set.insert(cg.nodes[ni].id);
+        }
+        for (int ni : mixers) z2set.insert(cg.nodes[ni].id);
+        if (!z2set.empty()) {
+            // (the same layout check as the zero variant's: without it the graph simply has no such unit)
+            std::set<int> all = zset;
+            all.insert(z2set.begin(), z2set.end());
+            bool same = false;
+            try {
+                const auto z = compile_pass(g_in, &all, &z2body);
+                same = z->n_slots == out.n_slots && z->state.size() == out.state.size() && z->n_ramps == out.n_ramps &&
+                       z->n_streams == out.n_streams && z->lpv == out.lpv && z->max_pipeline == out.max_pipeline && z->wide4 == out.wide4;
+                for (size_t i = 0; same && i < out.state.size(); ++i) same = z->state[i].name == out.state[i].name;
+            } catch (const std::exception&) {
+                same = false;
+            }
+            if (same) {
+                out.zero2_slots.assign(zeros.begin(), zeros.end());
+                out.finite_slots.assign(guards.begin(), guards.end());
+            } else {
+                z2set.clear();
+                z2body.clear();
+            }
+        }
+    }
     // the wide four-wave form: 16-frame chunks, flag hand-off over rings of two chunks (round 6; round 5: one barrier per chunk).
     // OGC_FLAGS="xch,depth" (experiment): `xch` frames per chunk, rings of `depth` chunks, depth 0 = the barrier
     std::string wide_args = "16, 2";
@@ -4880,6 +5089,29 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         zsrc << " (their consumers read the AddValue's value from its slot)." << pre.str() << "namespace og_gen_" << hs
              << "_z {\nconstexpr int LPV = " << out.lpv << "; // lanes per voice\n" << zbody << "} // namespace\n\n" << undefs;
     }
+    // the deeper zero variant's unit (csrc/gen/<graph>_z2.hip)
+    const bool zv2 = !z2body.empty();
+    std::ostringstream z2src;
+    if (zv2) {
+        z2src << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << g.name << "' -- do not edit.\n"
+              << "// The deeper zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroFolds): the same kernel for launches in which slot(s)";
+        for (int zs : out.zero2_slots) z2src << " " << zs;
+        z2src << " hold +-0,\n// slot(s)";
+        for (int fs : out.finite_slots) z2src << " " << fs;
+        z2src << " are finite and no ramp ticks.  Left out or folded:";
+        for (const NodeInst& n : cg.nodes)
+            if (zset.count(n.id) || z2set.count(n.id)) z2src << " " << n.decl->name;
+        z2src << "." << pre.str() << "namespace og_gen_" << hs << "_z2 {\nconstexpr int LPV = " << out.lpv << "; // lanes per voice\n" << z2body
+              << "} // namespace\n\n" << undefs;
+    }
+    // (the units of the zero variants: stream, suffix of the kernel names and of the namespace)
+    struct ZUnit {
+        std::ostringstream* os;
+        const char* sfx;
+    };
+    std::vector<ZUnit> zunits;
+    if (zv) zunits.push_back({&zsrc, "z"});
+    if (zv2) zunits.push_back({&z2src, "z2"});
     const char* variants[4][3] = {{"00", "false", "false"}, {"10", "true", "false"}, {"01", "false", "true"},
                                   {"11", "true", "true"}};
     // register budget of the ordinary kernel: 4 waves per SIMD = 128 VGPRs.  The 4-lanes-per-voice e-piano form
@@ -4893,17 +5125,17 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     int waves_eu = (out.lpv > 1 && out.lane_width == 8) ? 3 : 4;
     if (const char* ew = ogabi::experiment_knob("OGC_WAVES_EU")) waves_eu = std::max(1, std::min(8, atoi(ew)));
     // the zero variant: only next to the kernels that read no ramp table (`_00z`, `_01z`)
-    auto zero_variants = [&](const std::function<void(const char* v, const char* taps)>& f) {
-        if (zv)
+    auto zero_variants = [&](const std::function<void(std::ostringstream& zsrc, const char* z, const char* v, const char* taps)>& f) {
+        for (auto& u : zunits)
             for (auto& v : variants)
-                if (v[1][0] == 'f') f(v[0], v[2]);
+                if (v[1][0] == 'f') f(*u.os, u.sfx, v[0], v[2]);
     };
     for (auto& v : variants)
         src << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v[0]
             << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block<" << v[1] << ", " << v[2] << ">(A); }\n";
-    zero_variants([&](const char* v, const char* taps) {
+    zero_variants([&](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
         zsrc << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v
-            << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block<false, " << taps << ">(A); }\n";
+            << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block<false, " << taps << ">(A); }\n";
     });
     std::vector<std::pair<int, int>> depths; // (tag: what OgBlockArgs::split selects, waves per workgroup)
     if (!cg.groups2.empty()) depths.push_back({2, (int)cg.groups2.size()});
@@ -4921,32 +5153,33 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         // (the narrow four-wave form holds six workgroups per CU; left to itself the compiler gives the zero kernel 82 VGPRs
         // where the general one has 80 -- five waves per SIMD.  Held to six: 72 VGPRs, no spill)
         const std::string zbudget = (K == 4 && narrow_args.empty()) ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
-        zero_variants([&, K = K, W = W](const char* v, const char* taps) {
+        zero_variants([&, K = K, W = W](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
             zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * W << ")" << zbudget << " void og_k" << K << "_" << hs << "_" << v
-                << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block_p" << K << "<false, " << taps << narrow_args << ">(A); }\n";
+                << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block_p" << K << "<false, " << taps << narrow_args << ">(A); }\n";
         });
     }
     if (out.wide4) {
         for (auto& v : variants)
             src << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v[0]
                 << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block_p4<" << v[1] << ", " << v[2] << ", " << wide_args << ">(A); }\n";
-        zero_variants([&](const char* v, const char* taps) {
+        zero_variants([&](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
             zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v
-                << "z(OgBlockArgs A) { og_gen_" << hs << "_z::voice_block_p4<false, " << taps << ", " << wide_args << ">(A); }\n";
+                << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block_p4<false, " << taps << ", " << wide_args << ">(A); }\n";
         });
     }
     src << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
         << "static void og_launch_" << hs << "(const OgBlockArgs& A, bool ramps, bool taps, hipStream_t s)\n{\n"
         << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
-    if (zv)
-        zsrc << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
-             << "static void og_launch_" << hs << "_z(const OgBlockArgs& A, bool taps, hipStream_t s)\n{\n"
-             << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
+    for (auto& u : zunits)
+        *u.os << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
+              << "static void og_launch_" << hs << "_" << u.sfx << "(const OgBlockArgs& A, bool taps, hipStream_t s)\n{\n"
+              << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
     // the zero variant's launch of a shape (`kp`: the kernel name up to the hash), inside its `if (A.split ...) {`
     auto zero_branch = [&](const std::string& kp, const char* dims, const std::string& head) {
-        if (!zv) return;
-        zsrc << head << "        if (taps) hipLaunchKernelGGL(" << kp << hs << "_01z, " << dims << ", 0, s, A);\n"
-             << "        else hipLaunchKernelGGL(" << kp << hs << "_00z, " << dims << ", 0, s, A);\n" << (head.empty() ? "" : "        return;\n    }\n");
+        for (auto& u : zunits)
+            *u.os << head << "        if (taps) hipLaunchKernelGGL(" << kp << hs << "_01" << u.sfx << ", " << dims << ", 0, s, A);\n"
+                  << "        else hipLaunchKernelGGL(" << kp << hs << "_00" << u.sfx << ", " << dims << ", 0, s, A);\n"
+                  << (head.empty() ? "" : "        return;\n    }\n");
     };
     if (out.wide4) {
         const std::string head = std::string("    if (A.split == 4u && A.wide) { // four waves per 64 voices, 16-frame hand-offs\n") +
@@ -4970,10 +5203,12 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             << "        else hipLaunchKernelGGL(og_k" << K << "_" << hs << "_11, gk, bk, 0, s, A);\n"
             << "        return;\n    }\n";
     }
-    if (zv) {
-        zsrc << "    if (taps) hipLaunchKernelGGL(og_k_" << hs << "_01z, grid, block, 0, s, A);\n"
-             << "    else hipLaunchKernelGGL(og_k_" << hs << "_00z, grid, block, 0, s, A);\n}\n"
-             << "static const OgZeroKernelRegistrar og_zreg_" << hs << "(0x" << hs << "ull, &og_launch_" << hs << "_z);\n#endif\n";
+    for (auto& u : zunits) {
+        const bool deep = !strcmp(u.sfx, "z2"); // (the registry's tier 2; the zero variant registers as tier 1)
+        *u.os << "    if (taps) hipLaunchKernelGGL(og_k_" << hs << "_01" << u.sfx << ", grid, block, 0, s, A);\n"
+              << "    else hipLaunchKernelGGL(og_k_" << hs << "_00" << u.sfx << ", grid, block, 0, s, A);\n}\n"
+              << "static const OgZeroKernelRegistrar og_" << u.sfx << "reg_" << hs << "(0x" << hs << "ull, &og_launch_" << hs << "_" << u.sfx
+              << (deep ? ", 2" : "") << ");\n#endif\n";
     }
     src <<"    if (!ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_00, grid, block, 0, s, A);\n"
         << "    else if (ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_10, grid, block, 0, s, A);\n"
@@ -4991,6 +5226,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         << hs << ", &og_occ_" << hs << ");\n#endif\n";
     out.source = src.str();
     out.zero_source = zsrc.str();
+    out.zero2_source = z2src.str();
     return cgp;
 }
 

@@ -137,6 +137,7 @@ struct CompiledGraph {
     std::string name;
     std::string source; // complete HIP translation unit for this graph
     std::string zero_source; // ... and that of its zero variant (og_graph.cpp, ZeroChain; empty: none): csrc/gen/<graph>_z.hip
+    std::string zero2_source; // ... and that of its deeper zero variant (og_graph.cpp, ZeroFolds; empty: none): csrc/gen/<graph>_z2.hip
     uint64_t hash = 0;  // FNV-1a of the kernel body: AOT registry / JIT cache key
     std::vector<InputInfo> inputs;
     std::vector<StateWord> state;      // per-voice words
@@ -151,6 +152,9 @@ struct CompiledGraph {
     // the zero variant (og_graph.cpp, ZeroChain): slots whose values must all be +-0 for a launch to run og_k*_<hash>_{00,01}z
     // (empty: the graph has no such kernel)
     std::vector<int> zero_slots;
+    // the deeper zero variant (og_graph.cpp, ZeroFolds): a launch runs og_k*_<hash>_{00,01}z2 when every slot of zero2_slots
+    // (zero_slots included) holds +-0 and every slot of finite_slots holds a finite value (empty zero2_slots: no such kernel)
+    std::vector<int> zero2_slots, finite_slots;
     int valu_estimate = 0;             // estimated VALU instructions per frame of one wave of the ordinary kernel (node weights)
     // post-mix stage (electric-piano/src/main.rs:88-96): Tremolo on the summed bus -> Frame<2>
     bool bus_tremolo = false;

@@ -51,7 +51,7 @@ std::vector<char> compile_to_code(const ogc::CompiledGraph& cg, const char* arch
         srcs[i] = bodies[i].c_str();
     }
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source).c_str(), (cg.name + ".hip").c_str(), 3, srcs, names) != HIPRTC_SUCCESS)
+    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source + cg.zero2_source).c_str(), (cg.name + ".hip").c_str(), 3, srcs, names) != HIPRTC_SUCCESS)
         throw std::runtime_error("oscen jit: hiprtcCreateProgram failed");
     std::string archopt = std::string("--offload-arch=") + arch;
     const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-DOG_JIT=1"};
@@ -80,6 +80,8 @@ struct JitImpl : OgJitKernel {
     hipFunction_t fn4w[4] = {}; // ... with 16-frame hand-offs (when the graph has them)
     // the zero variant (og_graph.cpp, ZeroChain) of each shape, [taps]: only where the graph has one
     hipFunction_t fnz[2] = {}, fn2z[2] = {}, fn4z[2] = {}, fn4wz[2] = {};
+    // ... and the deeper zero variant (ZeroFolds)
+    hipFunction_t fnz2[2] = {}, fn2z2[2] = {}, fn4z2[2] = {}, fn4wz2[2] = {};
     unsigned lpv = 1;
     ~JitImpl() override
     {
@@ -93,6 +95,12 @@ struct JitImpl : OgJitKernel {
     {
         if (!fnz[0]) return OgJitKernel::launch_zero(args, taps, stream);
         run(args, taps ? 1 : 0, fnz, fn2z, fn4z, fn4wz, stream);
+        return true;
+    }
+    bool launch_zero2(const OgBlockArgs& args, bool taps, hipStream_t stream) override
+    {
+        if (!fnz2[0]) return false;
+        run(args, taps ? 1 : 0, fnz2, fn2z2, fn4z2, fn4wz2, stream);
         return true;
     }
     void run(const OgBlockArgs& args, int vi, const hipFunction_t* fn, const hipFunction_t* fn2, const hipFunction_t* fn4,
@@ -162,18 +170,25 @@ std::unique_ptr<OgJitKernel> og_jit_compile(const ogc::CompiledGraph& cg)
             }
         }
     }
+    auto get = [&](hipFunction_t* f, const std::string& name) {
+        if (hipModuleGetFunction(f, k->mod, name.c_str()) != hipSuccess)
+            throw std::runtime_error("oscen jit: kernel " + name + " not found in module");
+    };
+    auto get_unit = [&](const char* const* zvar, hipFunction_t* f, hipFunction_t* f2, hipFunction_t* f4, hipFunction_t* f4w) {
+        for (int i = 0; i < 2; ++i) {
+            get(&f[i], std::string("og_k_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 2) get(&f2[i], std::string("og_k2_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 4) get(&f4[i], std::string("og_k4_") + hs + "_" + zvar[i]);
+            if (cg.max_pipeline >= 4 && cg.wide4) get(&f4w[i], std::string("og_k4w_") + hs + "_" + zvar[i]);
+        }
+    };
     if (!cg.zero_slots.empty()) {
         const char* zvar[2] = {"00z", "01z"};
-        auto get = [&](hipFunction_t* f, const std::string& name) {
-            if (hipModuleGetFunction(f, k->mod, name.c_str()) != hipSuccess)
-                throw std::runtime_error("oscen jit: kernel " + name + " not found in module");
-        };
-        for (int i = 0; i < 2; ++i) {
-            get(&k->fnz[i], std::string("og_k_") + hs + "_" + zvar[i]);
-            if (cg.max_pipeline >= 2) get(&k->fn2z[i], std::string("og_k2_") + hs + "_" + zvar[i]);
-            if (cg.max_pipeline >= 4) get(&k->fn4z[i], std::string("og_k4_") + hs + "_" + zvar[i]);
-            if (cg.max_pipeline >= 4 && cg.wide4) get(&k->fn4wz[i], std::string("og_k4w_") + hs + "_" + zvar[i]);
-        }
+        get_unit(zvar, k->fnz, k->fn2z, k->fn4z, k->fn4wz);
+    }
+    if (!cg.zero2_slots.empty()) {
+        const char* zvar[2] = {"00z2", "01z2"};
+        get_unit(zvar, k->fnz2, k->fn2z2, k->fn4z2, k->fn4wz2);
     }
     return k;
 }

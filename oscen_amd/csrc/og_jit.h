@@ -19,6 +19,8 @@ struct OgJitKernel {
         launch(args, false, taps, stream);
         return false;
     }
+    // a launch of the deeper zero variant (og_graph.cpp, ZeroFolds).  Returns false, with nothing launched, where there is none.
+    virtual bool launch_zero2(const OgBlockArgs&, bool, hipStream_t) { return false; }
     virtual int occupancy(int depth) = 0; // resident workgroups per CU of the depth-1 / 2 / 4 shape (0: no such shape)
 };
 

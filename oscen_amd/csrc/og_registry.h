@@ -4,7 +4,9 @@
 // caller's graph description on the host, hashes the body it would generate
 // and looks the kernel up here (falling back to hiprtc for unknown graphs).
 // A graph's zero variant (csrc/gen/<graph>_z.hip, og_graph.cpp ZeroChain)
-// registers its launch function under the same hash in a registry of its own.
+// registers its launch function under the same hash in a registry of its own,
+// as tier 1; its deeper zero variant (csrc/gen/<graph>_z2.hip, ZeroFolds)
+// registers there as tier 2: the registry maps (hash, tier) to a launcher.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,18 +47,20 @@ struct OgKernelRegistrar {
 
 struct OgZeroKernelEntry {
     uint64_t hash;
+    int tier; // 1: the zero variant (`_z`), 2: the deeper zero variant (`_z2`)
     OgZeroLaunchFn launch;
     OgZeroKernelEntry* next;
 };
 
 OgZeroKernelEntry*& og_zero_kernel_registry_head();
-OgZeroLaunchFn og_find_zero_kernel(uint64_t hash);
+OgZeroLaunchFn og_find_zero_kernel(uint64_t hash, int tier = 1);
 
 struct OgZeroKernelRegistrar {
     OgZeroKernelEntry entry;
-    OgZeroKernelRegistrar(uint64_t hash, OgZeroLaunchFn fn)
+    OgZeroKernelRegistrar(uint64_t hash, OgZeroLaunchFn fn, int tier = 1)
     {
         entry.hash = hash;
+        entry.tier = tier;
         entry.launch = fn;
         entry.next = og_zero_kernel_registry_head();
         og_zero_kernel_registry_head() = &entry;
