@@ -53,6 +53,10 @@ extern "C" {
 extern "C" {
     pub fn og_graph_add_bus_node(g: *mut og_graph_desc, name: *const c_char, type_ctor: *const c_char,
                                  args: *const c_float, n_args: u32) -> c_int;
+    pub fn og_graph_add_bus_convolver(g: *mut og_graph_desc, name: *const c_char, ir_name: *const c_char) -> c_int;
+    pub fn og_register_ir(name: *const c_char, taps: *const c_float, n_taps: u32) -> c_int;
+    pub fn og_unregister_ir(name: *const c_char) -> c_int;
+    pub fn og_set_bus_ir(e: *mut og_engine, ir_name: *const c_char) -> c_int;
     pub fn og_graph_connect_via(g: *mut og_graph_desc, src: *const c_char, via: *const c_char,
                                 dst: *const c_char) -> c_int;
     pub fn og_graph_parse(dsl_text: *const c_char, per_voice_inputs: *const c_char,

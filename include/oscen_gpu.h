@@ -170,6 +170,18 @@ int og_unregister_graph_type(const char* type_name);
  * "node.output" -> "<second graph output>" (Frame<2>: the engine then has 2 channels). */
 int og_graph_add_bus_node(og_graph_desc* g, const char* name, const char* type_ctor, const float* args,
                           uint32_t n_args);
+/* Impulse responses by name: what `Convolver::with_ir(reverb_ir())` resolves -- the call's path as written or its last
+ * segment; parentheses and arguments are ignored.  Mono, at the session rate, copied; a name that exists is replaced;
+ * n_taps == 0 is legal (silence); at most 2^20 taps. */
+int og_register_ir(const char* name, const float* taps, uint32_t n_taps);
+int og_unregister_ir(const char* name);
+/* The post-mix Convolver (oscen-lib/src/convolution/mod.rs: the sample-exact full convolution, zero latency) on the summed
+ * voices: `name = Convolver::with_ir(ir_name())`, or, ir_name == NULL, `Convolver::new()` -- silent until og_set_bus_ir.
+ * Wired like the Tremolo: "<voice output name>" -> "name.input", "name.output" -> "<second graph output>".  The output has
+ * the channels of the voices (Frame<2> voices: the mono response on both channels).  One bus node per graph; a Convolver
+ * anywhere else (inside a voice graph, oversampled, in a feedback path) and a cluster over such a graph are
+ * OG_E_UNSUPPORTED. */
+int og_graph_add_bus_convolver(og_graph_desc* g, const char* name, const char* ir_name);
 int og_graph_connect(og_graph_desc* g, const char* src_expr, const char* dst, const char* policy);
 /* `src -> [via] -> dst` (oscen-graph-compiler/src/ir/lower.rs:342-347): route through a declared
  * Delay node, or, when `via` is a sample count ("64"), through an anonymous Delay::new(N, 0.0).
@@ -340,10 +352,17 @@ int og_output_channel(const og_engine* e, const char* name, uint32_t* offset, ui
 uint32_t og_num_voices(const og_engine* e);
 uint32_t og_latency_samples(const og_engine* e); /* emit_struct.rs:534-570 */
 /* The post-mix node of a wrapper graph (`voices.output -> tremolo.input`, electric-piano/src/main.rs:88-96): 0 = none,
- * 1 = a node that is LINEAR in its input (Tremolo: out = in * pan, tremolo.rs:40-62), 2 = any other.  A host that sums the
+ * 1 = a node that is LINEAR in its input (Tremolo: out = in * pan, tremolo.rs:40-62; Convolver), 2 = any other.  A host that sums the
  * buses of several engines itself (oscen_amd/distributed.py) may sum AFTER a linear post-mix stage; for kind 2 it must sum
  * the voice sums first and run the node once, as og_cluster_* does. */
 int og_post_mix_kind(const og_engine* e);
+/* Swap the post-mix Convolver's response for a registered one.  It takes effect at the first frame of the next block
+ * handed to the engine (it travels with the queued block: correct under og_set_bus_batching) with Convolver::process's
+ * crossfade (convolution/mod.rs:535-573): the new response starts on empty history, the old one keeps running for
+ * fade_len = max(1, round(0.02 sr)) samples, out = new sin(g pi/2) + old cos(g pi/2), g = pos / fade_len; a second swap
+ * during a fade drops the fading-out response at once.  og_init clears history and fade.  Allocates: not for the audio
+ * thread.  OG_E_INVALID on an engine without a post-mix Convolver or for an unregistered name. */
+int og_set_bus_ir(og_engine* e, const char* ir_name);
 uint64_t og_frames_processed(const og_engine* e);
 /* layout facts used by the roofline accounting */
 uint32_t og_state_words_per_voice(const og_engine* e);

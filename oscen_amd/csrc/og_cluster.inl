@@ -483,6 +483,8 @@ int og_cluster_create(const og_graph_desc* g, uint64_t n_voices_total, const int
                 throw std::runtime_error(g_err);
             }
             std::unique_ptr<og_engine> e(raw); // (owned here until the cluster has it: alloc_bus_buffers may throw)
+            if (e->cg->bus_stage == ogc::BusStage::Convolver) // (the stage would run once on the root, after the reduce: not built)
+                throw ogabi::Unsupported("a cluster over a graph with a post-mix Convolver is not supported in this version (the convolver runs on one device's bus)");
             e->bus_stage = false; // shards hand over the voice sum; the post-mix node runs once, on the root
             {
                 HIPCK(hipSetDevice(e->device));
@@ -503,7 +505,7 @@ int og_cluster_create(const og_graph_desc* g, uint64_t n_voices_total, const int
         }
         c->channels = c->shard[0]->cg->channels;
         c->vch = c->shard[0]->cg->voice_channels;
-        c->tremolo = c->shard[0]->cg->bus_tremolo;
+        c->tremolo = c->shard[0]->cg->bus_stage == ogc::BusStage::Tremolo;
         const size_t nd = c->devs.size();
         c->dev_stream.assign(nd, nullptr);
         for (int b = 0; b < 2; ++b) {

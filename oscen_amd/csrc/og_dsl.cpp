@@ -507,13 +507,17 @@ std::string to_dsl(const GraphDesc& g)
     o << "\nnodes {\n";
     for (const auto& n : g.nodes) {
         if (n.bus) {
-            o << "    // post-mix (bus) node: " << n.name << " = " << n.type << "()\n";
+            o << "    // post-mix (bus) node: " << n.name << " = " << n.type << "(";
+            for (size_t i = 0; i < n.args.size(); ++i) // (Convolver::with_ir(room()): the response's name is a raw argument)
+                o << (i ? ", " : "") << (i < n.raw_args.size() && !n.raw_args[i].empty() ? n.raw_args[i] : num(n.args[i]));
+            o << ")\n";
             continue;
         }
         if (n.name.rfind("__inline_delay_", 0) == 0) continue; // printed as `-> [N] ->`
         std::string ty = normalize_type(n.type); // "TptFilter<2>::new" prints as the Rust path TptFilter::<Frame<2>>::new
         const size_t lt = ty.find('<'), gt = ty.find(">::");
-        if (lt != std::string::npos && gt != std::string::npos && lt < gt)
+        // (a const generic that is no frame type -- `VoiceAllocator::<4>::new` -- is not normalised and prints as written)
+        if (lt != std::string::npos && gt != std::string::npos && lt < gt && lt > 0 && ty[lt - 1] != ':')
             ty = ty.substr(0, lt) + "::<Frame<" + ty.substr(lt + 1, gt - lt - 1) + ">>" + ty.substr(gt + 1);
         o << "    " << n.name << " = " << (n.array_len ? "[" : "") << ty << "(";
         for (size_t i = 0; i < n.args.size(); ++i)

@@ -27,6 +27,7 @@
 #include "og_jit.h"
 #include "og_math.h"
 #include "og_registry.h"
+#include "og_bus_conv.hip.h"
 
 // Sum the per-workgroup partial rows (fixed association, no atomics).
 // One workgroup per 16 frames, 64 row-slices x 16 frames = 1024 threads: thread (slice s, frame f) adds
@@ -432,6 +433,103 @@ struct og_engine {
     uint32_t ring_cap[OG_MAX_RINGS] = {0, 0, 0, 0};
     float* d_mono = nullptr;      // summed voices before the post-mix stage
     float* d_bus_phase = nullptr; // Tremolo.phase
+    // ---- post-mix Convolver (og_bus_conv.hip.h) ---------------------------------------------------
+    // A response lives on the device from og_set_bus_ir (or og_create) until the engine is destroyed or a later
+    // og_set_bus_ir finds the stream idle: launches already queued may still read it.
+    struct ConvIR {
+        float* d = nullptr;
+        std::vector<float> taps; // host copy (snapshots)
+        uint32_t K() const { return (uint32_t)taps.size(); }
+    };
+    // what a block is rendered under: the current response and, during the crossfade of a swap, the outgoing one; each with
+    // the frame its history is valid from (a new response only sees input from the swap frame on)
+    struct ConvCfg {
+        std::shared_ptr<ConvIR> cur, old;
+        uint64_t cur_from = 0, old_from = 0, fade_start = 0;
+        bool same(const ConvCfg& o) const
+        {
+            return cur == o.cur && old == o.old && cur_from == o.cur_from && old_from == o.old_from && fade_start == o.fade_start;
+        }
+    };
+    ConvCfg conv;                          // the state after the last queued block
+    std::shared_ptr<ConvIR> conv_pending;  // og_set_bus_ir: takes effect at the first frame of the next block
+    std::vector<ConvCfg> q_conv;           // configurations of the queued blocks (QueuedBlock::conv)
+    std::vector<float*> conv_bufs;         // every device tap buffer this engine holds (conv_gc frees the unused ones)
+    // history: interleaved frames, [hist_len][voice_channels]; the next batch's dry bus goes to frame hist_pos and at least
+    // hist_keep frames in front of it hold the input that came before (zeros before the first block)
+    float* d_hist = nullptr;
+    size_t hist_len = 0, hist_keep = 0, hist_pos = 0;
+    float* d_conv_rows = nullptr; // partial rows: [current | outgoing][segment][channel][conv_row_stride]
+    uint32_t conv_row_stride = 0;
+    size_t conv_rows_half = 0;
+    bool conv_on() const { return cg->bus_stage == ogc::BusStage::Convolver && bus_stage; }
+    uint32_t conv_fade_len() const { return (uint32_t)std::max(1.0f, roundf(0.02f * sr)); } // prepare(): CROSSFADE_SECONDS * sr, rounded, >= 1
+    std::shared_ptr<ConvIR> conv_upload(const float* taps, size_t n)
+    {
+        auto ir = std::make_shared<ConvIR>();
+        ir->taps.assign(taps, taps + n);
+        if (n) {
+            HIPCK(hipMalloc(&ir->d, n * 4));
+            conv_bufs.push_back(ir->d);
+            bounce.h2d(ir->d, ir->taps.data(), n * 4, stream);
+        }
+        return ir;
+    }
+    void conv_retire(std::shared_ptr<ConvIR>& ir) { ir.reset(); }
+    void conv_gc() // free the taps no response in use points at; only with nothing queued and the stream idle
+    {
+        if (!queue.empty() || hipStreamQuery(stream) != hipSuccess) return;
+        std::vector<float*> keep;
+        for (float* p : conv_bufs) {
+            bool used = false;
+            for (const ConvIR* ir : {conv.cur.get(), conv.old.get(), conv_pending.get()}) used = used || (ir && ir->d == p);
+            if (used) keep.push_back(p);
+            else (void)hipFree(p);
+        }
+        conv_bufs.swap(keep);
+    }
+    // (re)size the history and the partial rows for responses of up to need_hist + 1 taps and the current batch size,
+    // keeping the history; the stream is idle (callers launch the queue and wait first)
+    void conv_alloc(size_t need_hist)
+    {
+        const size_t vc = cg->voice_channels;
+        const size_t max_frames = (size_t)OG_MAX_BLOCK * batch_cap;
+        const size_t keep = std::max(hist_keep, (std::max<size_t>(need_hist, 1) + OG_CONV_S - 1) / OG_CONV_S * OG_CONV_S);
+        const size_t len = 2 * keep + 2 * max_frames;
+        if (!d_hist || keep != hist_keep || len != hist_len) {
+            float* n = nullptr;
+            HIPCK(hipMalloc(&n, len * vc * 4));
+            HIPCK(hipMemsetAsync(n, 0, len * vc * 4, stream));
+            if (d_hist) {
+                HIPCK(hipMemcpyAsync(n + (keep - hist_keep) * vc, d_hist + (hist_pos - hist_keep) * vc, hist_keep * vc * 4, hipMemcpyDeviceToDevice, stream));
+                HIPCK(hipStreamSynchronize(stream));
+                HIPCK(hipFree(d_hist));
+            }
+            d_hist = n;
+            hist_keep = keep;
+            hist_len = len;
+            hist_pos = keep;
+        }
+        const uint32_t stride = (uint32_t)((max_frames + 3) / 4 * 4);
+        const size_t half = (keep / OG_CONV_S + 1) * vc * stride;
+        if (!d_conv_rows || stride != conv_row_stride || half != conv_rows_half) {
+            if (d_conv_rows) HIPCK(hipFree(d_conv_rows));
+            d_conv_rows = nullptr;
+            HIPCK(hipMalloc(&d_conv_rows, 2 * half * 4));
+            conv_row_stride = stride;
+            conv_rows_half = half;
+        }
+        HIPCK(hipStreamSynchronize(stream));
+    }
+    void conv_reset() // prepare(): cleared history, no fade; the current response stays
+    {
+        if (!d_hist) return;
+        HIPCK(hipMemsetAsync(d_hist, 0, hist_len * cg->voice_channels * 4, stream));
+        hist_pos = hist_keep;
+        conv_retire(conv.old);
+        conv.cur_from = conv.old_from = conv.fade_start = 0;
+        q_conv.clear();
+    }
     OgEvent* d_events = nullptr;
     size_t ev_cap = 0;
     size_t ev_headroom_env = 0; // OSCEN_GPU_EV_HEADROOM at og_create (0 = unset)
@@ -460,6 +558,7 @@ struct og_engine {
         float* dst; // where the block's bus goes
         uint32_t frames;
         float trem_rate, trem_depth;
+        uint32_t conv; // index into q_conv (post-mix Convolver)
     };
     std::vector<QueuedBlock> queue;
     uint64_t q_frame0 = 0;   // absolute frame of the first queued block
@@ -710,6 +809,9 @@ struct og_engine {
         for (int k = 0; k < OG_MAX_RINGS; ++k) (void)hipFree(d_ring[k]);
         (void)hipFree(d_mono);
         (void)hipFree(d_bus_phase);
+        (void)hipFree(d_hist);
+        (void)hipFree(d_conv_rows);
+        for (float* p : conv_bufs) (void)hipFree(p);
         (void)hipFree(d_events);
         (void)hipFree(d_ev_end);
         (void)hipFree(d_ev_cursor);
@@ -761,6 +863,7 @@ struct og_engine {
             bounce.h2d(d_lane_state, limg.data(), limg.size() * 4, stream);
         }
         if (d_bus_phase) HIPCK(hipMemsetAsync(d_bus_phase, 0, 4, stream));
+        conv_reset();
         // prepare(): every Delay gets a fresh zeroed ring sized from the sample rate (delay/mod.rs:59-69)
         for (size_t k = 0; k < cg->rings.size(); ++k) {
             const uint32_t cap = cg->rings[k].capacity(sr);
@@ -1294,7 +1397,8 @@ struct og_engine {
         HIPCK(hipMemset(d_partials, 0, (size_t)n_wg * max_frames * 4 * vc));
         HIPCK(hipMalloc(&d_partials2, ((size_t)n_wg / OG_RED_GROUP + 2 + 64) * max_frames * 4));
         HIPCK(hipMalloc(&d_stage_bus, max_frames * OG_MAX_BUS_CHANNELS * 4));
-        if (cg->bus_tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
+        if (cg->bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
+        if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(std::max(conv.cur ? conv.cur->K() : 0u, conv.old ? conv.old->K() : 0u));
         const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
         for (int i = 0; i < RAMP_RING && rows; ++i) {
             if (d_ramp[i]) HIPCK(hipFree(d_ramp[i]));
@@ -1358,7 +1462,23 @@ struct og_engine {
         qb.dst = d_out ? d_out : d_bus;
         qb.frames = frames;
         qb.trem_rate = qb.trem_depth = 0.0f;
-        if (cg->bus_tremolo && bus_stage) { // voices.output -> tremolo.input; tremolo.output -> out (Frame<2>)
+        qb.conv = 0;
+        if (conv_on()) { // voices.output -> reverb.input; reverb.output -> out
+            // Convolver::process (convolution/mod.rs:535-573): the outgoing response is dropped once pos reaches fade_len; a
+            // swap retires a response that is still fading out at once and fades from the current one, which keeps its history
+            if (conv.old && frame_now >= conv.fade_start + conv_fade_len()) conv_retire(conv.old);
+            if (conv_pending) {
+                conv_retire(conv.old);
+                conv.old = conv.cur;
+                conv.old_from = conv.cur_from;
+                conv.cur = conv_pending;
+                conv.cur_from = conv.fade_start = frame_now;
+                conv_pending.reset();
+            }
+            if (q_conv.empty() || !q_conv.back().same(conv)) q_conv.push_back(conv);
+            qb.conv = (uint32_t)q_conv.size() - 1;
+        }
+        if (cg->bus_stage == ogc::BusStage::Tremolo && bus_stage) { // voices.output -> tremolo.input; tremolo.output -> out (Frame<2>)
             ogc::UEnv ev = env();
             qb.trem_rate = cg->tremolo_rate(ev);
             qb.trem_depth = cg->tremolo_depth(ev);
@@ -1487,12 +1607,22 @@ struct og_engine {
         }
         HIPCK(hipGetLastError());
         // ---- bus: sum the partial rows ----------------------------------------------------------------
-        const bool post_mix = cg->bus_tremolo && bus_stage;
+        const bool post_mix = cg->bus_stage == ogc::BusStage::Tremolo && bus_stage;
+        const bool post_conv = conv_on();
         const uint32_t ch = cg->voice_channels; // summed voices: mono, or Frame<2> voices (a post-mix node writes its Frame<2> bus itself)
         bool contiguous = !post_mix;
         for (size_t k = 1; k < queue.size() && contiguous; ++k)
             contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * ch;
         float* sum_dst = post_mix ? d_mono : (contiguous ? queue[0].dst : d_stage_bus);
+        float* const wet_dst = sum_dst;
+        if (post_conv) { // the dry sum goes behind the history; when the buffer is full the newest hist_keep frames move to its front
+            if (hist_pos + q_frames > hist_len) {
+                const uint32_t n = (uint32_t)(hist_keep * ch);
+                hipLaunchKernelGGL(og_bus_conv_move, dim3((n + 255) / 256), dim3(256), 0, stream, d_hist + (hist_pos - hist_keep) * ch, d_hist, n);
+                hist_pos = hist_keep;
+            }
+            sum_dst = d_hist + hist_pos * ch;
+        }
         for (uint32_t c = 0; c < ch; ++c) { // one tree per channel plane; the last pass interleaves Frame<2> samples
             const float* src = d_partials + (size_t)c * A.partial_plane;
             uint32_t rows = n_wg;
@@ -1509,6 +1639,42 @@ struct og_engine {
             hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
         }
         HIPCK(hipGetLastError());
+        if (post_conv) { // one pass per run of blocks queued under the same responses -- as a rule the whole batch
+            const uint32_t fade_len = conv_fade_len();
+            for (size_t b0 = 0, f0 = 0; b0 < queue.size();) {
+                size_t b1 = b0;
+                uint32_t nf = 0;
+                while (b1 < queue.size() && queue[b1].conv == queue[b0].conv) nf += queue[b1++].frames;
+                const ConvCfg& cf = q_conv[queue[b0].conv];
+                const uint64_t t0 = q_frame0 + f0;
+                const int64_t buf_lo = -(int64_t)(hist_pos + f0);
+                auto response = [&](const std::shared_ptr<ConvIR>& ir, uint64_t from, uint32_t frames, float* rows) {
+                    OgConvResponse r;
+                    r.taps = ir ? ir->d : nullptr;
+                    r.n_taps = ir ? ir->K() : 0u;
+                    r.n_frames = frames;
+                    r.lo = (int32_t)std::max<int64_t>(buf_lo, from >= t0 ? (int64_t)std::min<uint64_t>(from - t0, 0x7fffffffu) : -(int64_t)std::min<uint64_t>(t0 - from, 0x7fffffffu));
+                    r.rows = rows;
+                    return r;
+                };
+                const uint64_t fade_end = cf.fade_start + fade_len;
+                const OgConvResponse rc = response(cf.cur, cf.cur_from, nf, d_conv_rows);
+                const OgConvResponse ro = response(cf.old, cf.old_from, (cf.old && t0 < fade_end) ? (uint32_t)std::min<uint64_t>(nf, fade_end - t0) : 0u,
+                                                   d_conv_rows + conv_rows_half);
+                const float* x = d_hist + (hist_pos + f0) * ch;
+                for (const OgConvResponse* r : {&rc, &ro})
+                    if (r->n_frames && r->n_taps)
+                        hipLaunchKernelGGL(og_bus_conv, dim3((r->n_frames + OG_CONV_F - 1) / OG_CONV_F, (r->n_taps + OG_CONV_S - 1) / OG_CONV_S, ch),
+                                           dim3(OG_CONV_LANES), 0, stream, x, ch, *r, conv_row_stride);
+                hipLaunchKernelGGL(og_bus_conv_finish, dim3((nf + 255) / 256, ch), dim3(256), 0, stream, rc, ro, ch, conv_row_stride,
+                                   (uint32_t)(t0 - cf.fade_start), fade_len, wet_dst + f0 * ch);
+                b0 = b1;
+                f0 += nf;
+            }
+            hist_pos += q_frames;
+            q_conv.clear();
+            HIPCK(hipGetLastError());
+        }
         size_t off = 0;
         for (const QueuedBlock& qb : queue) {
             if (post_mix) {
@@ -1775,6 +1941,40 @@ int og_graph_add_bus_node(og_graph_desc* g, const char* name, const char* type_c
     int rc = og_graph_add_node(g, name, type_ctor, args, n_args, 1);
     if (rc >= 0) g->g.nodes.back().bus = true;
     return rc;
+}
+
+int og_graph_add_bus_convolver(og_graph_desc* g, const char* name, const char* ir_name)
+{
+    return ogabi::guard([&]() -> int {
+    if (!g || !name) return set_err(OG_E_INVALID, "null argument");
+    ogc::GNode n;
+    n.name = name;
+    n.type = ir_name ? "Convolver::with_ir" : "Convolver::new";
+    if (ir_name) { // the response's name travels as the raw text of the constructor argument, as the DSL front end leaves it
+        n.args.push_back(0.0f);
+        n.raw_args.push_back(std::string(ir_name).find('(') == std::string::npos ? std::string(ir_name) + "()" : std::string(ir_name));
+    }
+    n.bus = true;
+    g->g.nodes.push_back(n);
+    return (int)g->g.nodes.size() - 1;
+    });
+}
+
+int og_register_ir(const char* name, const float* taps, uint32_t n_taps)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name || (n_taps && !taps)) return set_err(OG_E_INVALID, "null argument");
+    ogc::register_ir(name, taps, n_taps);
+    return OG_OK;
+    });
+}
+
+int og_unregister_ir(const char* name)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name) return set_err(OG_E_INVALID, "null argument");
+    return ogc::unregister_ir(name) ? OG_OK : set_err(OG_E_INVALID, std::string("no impulse response '") + name + "'");
+    });
 }
 
 int og_graph_connect(og_graph_desc* g, const char* src, const char* dst, const char* policy)
@@ -2055,7 +2255,9 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             // (+ one wave's worth of lane words behind the last plane: OgBlockArgs::lane_dump, where a lane beyond the last
             //  voice writes what an event handler of an array-valued node writes through its state planes)
             HIPCK(hipMalloc(&e->d_lane_state, cg.lane_state.size() * (size_t)n_voices * cg.lpv * cg.lane_width * 4 + (size_t)OG_WAVE * OG_LANE_DUMP_WORDS * 4));
-        if (cg.bus_tremolo) HIPCK(hipMalloc(&e->d_bus_phase, 4));
+        if (cg.bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&e->d_bus_phase, 4));
+        if (cg.bus_stage == ogc::BusStage::Convolver) // Convolver::with_ir(..) / ::new(): the empty response
+            e->conv.cur = e->conv_upload(cg.bus_ir ? cg.bus_ir->data() : nullptr, cg.bus_ir ? cg.bus_ir->size() : 0);
         HIPCK(hipMalloc(&e->d_ev_end, (size_t)n_voices * 4));
         HIPCK(hipMalloc(&e->d_ev_cursor, (size_t)n_voices * 4));
         HIPCK(hipMemset(e->d_ev_end, 0, (size_t)n_voices * 4));
@@ -2110,6 +2312,26 @@ int og_init(og_engine* e, float sample_rate)
             e->rcp_cover(e->release_need(slots.data()));
         }
         e->inited = true;
+        return OG_OK;
+    });
+}
+
+int og_set_bus_ir(og_engine* e, const char* ir_name)
+{
+    if (!e || !ir_name) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        if (!e->conv_on()) return set_err(OG_E_INVALID, "og_set_bus_ir: this engine has no post-mix Convolver");
+        std::string resolved;
+        const auto taps = ogc::lookup_ir(ir_name, &resolved);
+        if (!taps) return set_err(OG_E_INVALID, "unknown impulse response '" + resolved + "'; responses are registered with og_register_ir");
+        HIPCK(hipSetDevice(e->device));
+        if (taps->size() > e->hist_keep + 1) { // a longer response than the buffers were sized for (not a real-time path)
+            e->flush_bus();
+            HIPCK(hipStreamSynchronize(e->stream));
+            e->conv_alloc(taps->size());
+        }
+        e->conv_gc();
+        e->conv_pending = e->conv_upload(taps->data(), taps->size()); // replaces a swap no block has picked up yet
         return OG_OK;
     });
 }
@@ -2609,8 +2831,9 @@ int og_output_channel(const og_engine* e, const char* name, uint32_t* offset, ui
 }
 uint32_t og_num_voices(const og_engine* e) { return e ? e->V : 0; }
 uint32_t og_latency_samples(const og_engine* e) { return e ? e->cg->latency_samples : 0; }
-// (Tremolo is the only post-mix node type the compiler takes -- og_graph.cpp, bus nodes -- and it is linear in its input)
-int og_post_mix_kind(const og_engine* e) { return (e && e->cg->bus_tremolo) ? 1 : 0; }
+// (Tremolo and Convolver are the post-mix node types the compiler takes -- og_graph.cpp, bus nodes -- and both are linear in
+// their input)
+int og_post_mix_kind(const og_engine* e) { return (e && e->cg->bus_stage != ogc::BusStage::None) ? 1 : 0; }
 uint64_t og_frames_processed(const og_engine* e) { return e ? e->frame_now : 0; }
 uint32_t og_state_words_per_voice(const og_engine* e)
 {
@@ -2957,11 +3180,32 @@ struct SnapEvent {
     uint32_t block_local;
 };
 constexpr uint32_t SNAP_MAGIC = 0x3253474Fu; // "OGS2"
+// Post-mix Convolver: a section of its own BEHIND everything else (its size depends on the live responses, which a blob
+// brings along): header, taps of the current response, taps of the outgoing one, then the history -- the last
+// max(K) - 1 frames of the dry bus, interleaved.  A swap that no block has picked up yet is not part of the state.
+struct SnapConv {
+    uint32_t magic, channels;
+    uint32_t k_cur, k_old; // k_old = 0xFFFFFFFF: no fade in progress
+    uint64_t cur_from, old_from, fade_start;
+    uint32_t hist_frames, reserved;
+};
+constexpr uint32_t SNAP_CONV_MAGIC = 0x56434E4Fu; // "ONCV"
+size_t conv_hist_frames(const og_engine* e)
+{
+    const uint32_t k = std::max(e->conv.cur ? e->conv.cur->K() : 0u, e->conv.old ? e->conv.old->K() : 0u);
+    return k ? k - 1 : 0;
+}
+size_t conv_bytes(const og_engine* e)
+{
+    if (!e->conv_on()) return 0;
+    return sizeof(SnapConv) + ((size_t)(e->conv.cur ? e->conv.cur->K() : 0u) + (e->conv.old ? e->conv.old->K() : 0u) +
+                               conv_hist_frames(e) * e->cg->voice_channels) * 4;
+}
 
 size_t dsp_bytes(const og_engine* e)
 {
     return (e->cg->state.size() + e->cg->lane_state.size() * e->cg->lpv * e->cg->lane_width) * (size_t)e->V * 4 +
-           (e->cg->bus_tremolo ? 4 : 0) + e->ring_bytes();
+           (e->cg->bus_stage == ogc::BusStage::Tremolo ? 4 : 0) + e->ring_bytes();
 }
 // Every event that has not fired by frame_now.  Blocks that are still queued (og_set_bus_batching) consume the events
 // in [q_frame0, frame_now) when they are launched, and the snapshot header stores the post-queue frame_now: those
@@ -3000,7 +3244,7 @@ size_t og_state_bytes(const og_engine* e)
     if (!e) return 0;
     std::vector<SnapEvent> evs;
     collect_unconsumed(e, evs);
-    return dsp_bytes(e) + control_bytes(e, evs.size());
+    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e);
     });
 }
 
@@ -3012,7 +3256,7 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
         e->flush_bus(); // queued blocks consume their events first: what is collected below is what frame_now has not reached
         std::vector<SnapEvent> evs;
         collect_unconsumed(e, evs);
-        if (cap < dsp_bytes(e) + control_bytes(e, evs.size())) throw std::runtime_error("buffer too small");
+        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e)) throw std::runtime_error("buffer too small");
         const size_t a = e->cg->state.size() * (size_t)e->V * 4, b = e->cg->lane_state.size() * (size_t)e->V * e->cg->lpv * e->cg->lane_width * 4;
         e->bounce.d2h(dst, e->d_state, a, e->stream);
         if (b) e->bounce.d2h((char*)dst + a, e->d_lane_state, b, e->stream);
@@ -3038,6 +3282,20 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
         if (!evs.empty()) memcpy(p, evs.data(), evs.size() * sizeof(SnapEvent));
         p += evs.size() * sizeof(SnapEvent);
         if (!e->phys_of.empty()) memcpy(p, e->phys_of.data(), (size_t)e->V * sizeof(uint32_t));
+        p += e->phys_of.empty() ? 0 : (size_t)e->V * sizeof(uint32_t);
+        if (e->conv_on()) {
+            const auto& cv = e->conv;
+            const uint32_t kc = cv.cur ? cv.cur->K() : 0u, ko = cv.old ? cv.old->K() : 0u;
+            const size_t hf = conv_hist_frames(e), vc = e->cg->voice_channels;
+            const SnapConv sc{SNAP_CONV_MAGIC, (uint32_t)vc, kc, cv.old ? ko : 0xFFFFFFFFu, cv.cur_from, cv.old_from, cv.fade_start, (uint32_t)hf, 0u};
+            memcpy(p, &sc, sizeof sc);
+            p += sizeof sc;
+            if (kc) memcpy(p, cv.cur->taps.data(), (size_t)kc * 4);
+            p += (size_t)kc * 4;
+            if (ko) memcpy(p, cv.old->taps.data(), (size_t)ko * 4);
+            p += (size_t)ko * 4;
+            if (hf) e->bounce.d2h(p, e->d_hist + (e->hist_pos - hf) * vc, hf * vc * 4, e->stream); // (hf <= hist_keep <= hist_pos)
+        }
         return OG_OK;
     });
 }
@@ -3054,8 +3312,23 @@ int og_load_state(og_engine* e, const void* src, size_t len)
     const bool grouped = h.version == 3u;
     const size_t fixed = control_bytes(e, 0, grouped);
     if (h.magic != SNAP_MAGIC || (h.version != 2u && h.version != 3u) || h.n_inputs != e->cg->inputs.size() || len < dsp + fixed ||
-        h.n_events > (uint64_t)((len - dsp - fixed) / sizeof(SnapEvent)) || len != dsp + control_bytes(e, (size_t)h.n_events, grouped))
+        h.n_events > (uint64_t)((len - dsp - fixed) / sizeof(SnapEvent)) || len < dsp + control_bytes(e, (size_t)h.n_events, grouped))
         return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
+    const size_t full_len = len;
+    len = dsp + control_bytes(e, (size_t)h.n_events, grouped); // what follows is the post-mix Convolver's section
+    SnapConv sc{};
+    if (e->conv_on()) {
+        bool ok = full_len - len >= sizeof sc;
+        if (ok) memcpy(&sc, (const char*)src + len, sizeof sc);
+        ok = ok && sc.magic == SNAP_CONV_MAGIC && sc.channels == e->cg->voice_channels && sc.k_cur <= ogc::MAX_IR_TAPS &&
+             (sc.k_old == 0xFFFFFFFFu || sc.k_old <= ogc::MAX_IR_TAPS);
+        const uint64_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old, kmax = std::max<uint64_t>(sc.k_cur, ko);
+        ok = ok && sc.hist_frames == (kmax ? kmax - 1 : 0) &&
+             full_len - len == sizeof sc + ((size_t)sc.k_cur + ko + (size_t)sc.hist_frames * sc.channels) * 4;
+        if (!ok) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
+    } else if (full_len != len) {
+        return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
+    }
     std::vector<uint32_t> new_phys, new_logical;
     if (grouped) { // the voice order must be a permutation before anything is changed
         new_phys.resize(e->V);
@@ -3096,6 +3369,24 @@ int og_load_state(og_engine* e, const void* src, size_t len)
         }
         e->reset_timeline();
         HIPCK(hipStreamSynchronize(e->stream));
+        if (e->conv_on()) {
+            const size_t vc = e->cg->voice_channels;
+            const size_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old;
+            const float* q = (const float*)((const char*)src + len + sizeof sc);
+            if (sc.hist_frames > e->hist_keep) e->conv_alloc(sc.hist_frames);
+            e->conv.cur = e->conv_upload(q, sc.k_cur);
+            e->conv.old = sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + sc.k_cur, ko);
+            e->conv.cur_from = sc.cur_from;
+            e->conv.old_from = sc.old_from;
+            e->conv.fade_start = sc.fade_start;
+            e->conv_pending.reset();
+            HIPCK(hipMemsetAsync(e->d_hist, 0, e->hist_len * vc * 4, e->stream));
+            e->hist_pos = e->hist_keep;
+            if (sc.hist_frames)
+                e->bounce.h2d(e->d_hist + (e->hist_pos - sc.hist_frames) * vc, q + sc.k_cur + ko, (size_t)sc.hist_frames * vc * 4, e->stream);
+            HIPCK(hipStreamSynchronize(e->stream));
+            e->conv_gc();
+        }
         const bool order_changed = e->phys_of != new_phys;
         e->phys_of.swap(new_phys); // (version 2: identity)
         e->logical_of.swap(new_logical);

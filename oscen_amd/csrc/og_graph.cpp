@@ -378,6 +378,11 @@ std::map<std::string, UserFunction>& function_registry()
     static std::map<std::string, UserFunction> R;
     return R;
 }
+std::map<std::string, std::shared_ptr<const std::vector<float>>>& ir_registry()
+{
+    static std::map<std::string, std::shared_ptr<const std::vector<float>>> R;
+    return R;
+}
 const UserFunction* lookup_function(const std::string& path, const std::string& last)
 {
     auto& R = function_registry();
@@ -1774,6 +1779,12 @@ const std::map<std::string, NodeTypeInfo>& registry()
                                     {"output"}, emit_ep_bank, 0, 0, 8};
         // post-mix only (og_graph_add_bus_node): examples/electric-piano/src/tremolo.rs
         r["Tremolo::new"] = {{{"input", S, 0, -1}, {"rate", V, 5.0f, -1}, {"depth", V, 0.5f, -1}}, {"output"}, nullptr, 0, 0};
+        // post-mix only (og_graph_add_bus_convolver / the wrapper shape): oscen-lib/src/convolution/mod.rs.  The response is a
+        // NAME (raw constructor argument) resolved against the registry at lowering; <N>: Convolver::<Frame<N>>
+        for (const char* w : {"", "<2>", "<3>", "<4>"}) {
+            r[std::string("Convolver") + w + "::with_ir"] = {{{"input", S, 0, -1}}, {"output"}, nullptr, 0, 1};
+            r[std::string("Convolver") + w + "::new"] = {{{"input", S, 0, -1}}, {"output"}, nullptr, 0, 0};
+        }
         return r;
     }();
     return R;
@@ -2771,6 +2782,45 @@ void register_user_function(const UserFunction& f)
 }
 bool unregister_user_function(const std::string& name) { return function_registry().erase(name) > 0; }
 
+namespace {
+// `audio::reverb_ir(48000.0)` -> "audio::reverb_ir"
+std::string ir_call_path(const std::string& text)
+{
+    std::string t = text.substr(0, text.find('('));
+    t.erase(std::remove_if(t.begin(), t.end(), [](char ch) { return isspace((unsigned char)ch); }), t.end());
+    return t;
+}
+} // namespace
+void register_ir(const std::string& name, const float* taps, size_t n_taps)
+{
+    size_t b = 0;
+    for (;;) { // every path segment an identifier, like a function's name
+        const size_t c = name.find("::", b);
+        if (!is_ident(name.substr(b, c == std::string::npos ? std::string::npos : c - b))) fail("impulse response name '" + name + "' is not a path of identifiers");
+        if (c == std::string::npos) break;
+        b = c + 2;
+    }
+    if (n_taps > MAX_IR_TAPS) fail_unsupported("impulse response '" + name + "': " + std::to_string(n_taps) + " taps (at most " + std::to_string(MAX_IR_TAPS) + ")");
+    ir_registry()[name] = std::make_shared<const std::vector<float>>(taps, taps + n_taps);
+}
+bool unregister_ir(const std::string& name) { return ir_registry().erase(name) > 0; }
+std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved)
+{
+    const std::string path = ir_call_path(call_text);
+    const size_t c = path.rfind("::");
+    const std::string last = c == std::string::npos ? path : path.substr(c + 2);
+    if (resolved) *resolved = path;
+    auto& R = ir_registry();
+    auto it = R.find(path); // as written, then by its last segment, then a registration under a longer path (lookup_function)
+    if (it == R.end()) it = R.find(last);
+    if (it == R.end())
+        for (auto& kv : R) {
+            const std::string& k = kv.first;
+            if (k.size() > last.size() + 2 && k.compare(k.size() - last.size() - 2, std::string::npos, "::" + last) == 0) return kv.second;
+        }
+    return it == R.end() ? nullptr : it->second;
+}
+
 void register_user_node(const UserNodeType& t)
 {
     if (t.type.empty()) fail("node type needs a name");
@@ -3200,13 +3250,18 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
 
     // ---- nodes ------------------------------------------------------------------
     cg.nodes.resize(g.nodes.size());
+    int bus_conv_width = 1; // Convolver::<Frame<N>>: the N written in the node's type
     for (size_t i = 0; i < g.nodes.size(); ++i) {
         const GNode& nd = g.nodes[i];
         if (cg.node_by_name.count(nd.name) || cg.input_by_name.count(nd.name))
             fail("duplicate name '" + nd.name + "'");
         const NodeTypeInfo* nti = lookup_type(nd.type);
         if (!nti) fail("unknown node type '" + nd.type + "' (node '" + nd.name + "'); custom nodes are added with og_register_node");
-        for (size_t a = 0; a < nd.raw_args.size(); ++a)
+        const bool convolver = normalize_type(nd.type).rfind("Convolver", 0) == 0 && !nti->user;
+        if (convolver && !nd.bus)
+            fail_unsupported("node '" + nd.name + "': a Convolver is only available as the post-mix (bus) node, fed by the summed voices -- not inside a "
+                             "voice graph, oversampled or in a feedback path");
+        for (size_t a = 0; a < nd.raw_args.size() && !convolver; ++a)
             if (!nd.raw_args[a].empty())
                 fail("node '" + nd.name + "': constructor argument '" + nd.raw_args[a] + "' of " + nd.type + " is not a number");
         if (nd.args.size() != nti->nargs)
@@ -3224,12 +3279,27 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         cg.nodes[i].type = nti;
         cg.nodes[i].id = (int)i;
         if (nd.bus) {
-            if (nd.type != "Tremolo::new") fail_unsupported("only Tremolo::new is available as a post-mix (bus) node in this version");
-            if (out.bus_tremolo) fail_unsupported("only one post-mix (bus) node is supported in this version");
-            out.bus_tremolo = true;
-            out.channels = 2; // Frame<2>
-            out.tremolo_rate = [](const UEnv&) { return 5.0f; };  // Tremolo::new() defaults, tremolo.rs:27-37
-            out.tremolo_depth = [](const UEnv&) { return 0.5f; };
+            if (nd.type != "Tremolo::new" && !convolver)
+                fail_unsupported("only Tremolo::new and Convolver::new / ::with_ir are available as a post-mix (bus) node in this version");
+            if (out.bus_stage != BusStage::None) fail_unsupported("only one post-mix (bus) node is supported in this version");
+            if (convolver) {
+                if (nd.rate_factor != 1) fail_unsupported("node '" + nd.name + "': an oversampled Convolver is not supported");
+                out.bus_stage = BusStage::Convolver; // (channels: those of the voice sum, known once the outputs are formed)
+                const std::string ty = normalize_type(nd.type);
+                const size_t lt = ty.find('<');
+                bus_conv_width = lt == std::string::npos ? 1 : atoi(ty.c_str() + lt + 1);
+                if (nti->nargs == 1) {
+                    const std::string raw = nd.raw_args.empty() ? std::string() : nd.raw_args[0];
+                    if (raw.empty()) fail("node '" + nd.name + "': Convolver::with_ir takes the name of a registered impulse response (og_register_ir)");
+                    out.bus_ir = lookup_ir(raw, &out.bus_ir_name);
+                    if (!out.bus_ir) fail("unknown impulse response '" + out.bus_ir_name + "' (node '" + nd.name + "'); responses are registered with og_register_ir");
+                }
+            } else {
+                out.bus_stage = BusStage::Tremolo;
+                out.channels = 2; // Frame<2>
+                out.tremolo_rate = [](const UEnv&) { return 5.0f; };  // Tremolo::new() defaults, tremolo.rs:27-37
+                out.tremolo_depth = [](const UEnv&) { return 0.5f; };
+            }
         } else if (!nti->emit) {
             fail("node type '" + nd.type + "' can only be used as a post-mix (bus) node");
         }
@@ -3378,6 +3448,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         // ---- post-mix (bus) stage: `voices.output -> tremolo.input; v -> tremolo.depth; tremolo.output -> out`
         const int bdst = bus_node_of(e.dst), bsrc = bus_node_of(e.src);
         if (bdst >= 0 || bsrc >= 0) {
+            if (e.feedback) fail_unsupported("a post-mix (bus) node cannot be part of a feedback path ('" + e.src + " -> " + e.dst + "')");
             if (bsrc >= 0) {
                 auto oit = cg.output_by_name.find(e.dst);
                 if (oit == cg.output_by_name.end()) fail("a bus node can only feed a graph output ('" + e.dst + "')");
@@ -3390,6 +3461,8 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                 if (oit == cg.output_by_name.end())
                     fail("bus node input must be fed by the voice graph's output name (the summed voices), got '" + e.src + "'");
                 bus_src_output = oit->second;
+            } else if (out.bus_stage == BusStage::Convolver) {
+                fail("bus node has no input '" + port + "'");
             } else if (port == "rate" || port == "depth") {
                 Val v = cg.eval(Parser(e.src).parse());
                 if (!v.host) fail("bus node parameter '" + e.dst + "' must be a block-uniform value");
@@ -3526,7 +3599,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     }
     for (size_t i = 0; i < g.nodes.size(); ++i)
         if (g.nodes[i].bus) cg.nodes[i].live = false;
-    if (out.bus_tremolo && (bus_src_output < 0 || bus_final_output < 0))
+    if (out.bus_stage != BusStage::None && (bus_src_output < 0 || bus_final_output < 0))
         fail("the post-mix node must be wired `<voice output> -> node.input` and `node.output -> <graph output>`");
     for (size_t i = 0; i < g.nodes.size(); ++i)
         if (cg.nodes[i].live) out.lpv = std::max(out.lpv, cg.nodes[i].type->lpv);
@@ -3706,7 +3779,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             int n_stream_outs = 0;
             for (size_t oi = 0; oi < g.outputs.size(); ++oi)
                 if (g.outputs[oi].kind == Kind::Stream && out_edges.count((int)oi) && (int)oi != bus_src_output) ++n_stream_outs;
-            if (n_stream_outs > 1 && !out.bus_tremolo) stereo_out = true;
+            if (n_stream_outs > 1 && out.bus_stage != BusStage::Tremolo) stereo_out = true;
         }
         bool want = !(env_split && atoi(env_split) == 0) && cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
                     !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
@@ -4001,7 +4074,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                          " and " + (w > 1 ? "Frame<" + std::to_string(w) + ">" : std::string("f32")) + " sources");
                 width = w;
                 if (w > 1) {
-                    if (out.bus_tremolo) // (array-valued voices: the voice's lead lane puts every channel, og::bus_put)
+                    if (out.bus_stage == BusStage::Tremolo) // (array-valued voices: the voice's lead lane puts every channel, og::bus_put)
                         fail_unsupported("a Frame<N> graph output is not supported in post-mix graphs yet");
                     if (k == 0) acc.assign((size_t)w, std::string());
                     for (int c = 0; c < w; ++c) acc[(size_t)c] = (k == 0) ? v.ch[(size_t)c].e : "(" + acc[(size_t)c] + " + " + v.ch[(size_t)c].e + ")";
@@ -4056,7 +4129,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                 chans.push_back(var);
             }
         }
-        if (chans.size() > 1 && out.bus_tremolo)
+        if (chans.size() > 1 && out.bus_stage == BusStage::Tremolo)
             fail_unsupported("several bus channels (stream outputs / Frame<2>) are not supported in post-mix graphs yet");
         if (chans.size() > 4) fail("the mix bus carries at most 4 channels (stream outputs, a Frame<N> counting N)");
         if (chans.size() == 1) {
@@ -4072,6 +4145,9 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         }
         (void)n_stream;
     }
+    if (out.bus_stage == BusStage::Convolver && bus_conv_width > 1 && (uint32_t)bus_conv_width != out.voice_channels)
+        fail("the post-mix Convolver is a Convolver::<Frame<" + std::to_string(bus_conv_width) + ">> but the summed voices have " +
+             std::to_string(out.voice_channels) + " channel(s)");
     out.can_split = cg.split;
     out.max_pipeline = !cg.groups4.empty() ? 4 : (!cg.groups2.empty() ? 2 : 1);
 

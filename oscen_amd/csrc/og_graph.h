@@ -133,6 +133,7 @@ struct RingSpec { // a per-voice delay line in HBM (Delay's RingBuffer, delay/mo
     // next_power_of_two(min((2.0 * sr) as usize, 88200))
     uint32_t capacity(float graph_sr) const;
 };
+enum class BusStage { None = 0, Tremolo = 1, Convolver = 2 };
 struct CompiledGraph {
     std::string name;
     std::string source; // complete HIP translation unit for this graph
@@ -156,9 +157,12 @@ struct CompiledGraph {
     // (zero_slots included) holds +-0 and every slot of finite_slots holds a finite value (empty zero2_slots: no such kernel)
     std::vector<int> zero2_slots, finite_slots;
     int valu_estimate = 0;             // estimated VALU instructions per frame of one wave of the ordinary kernel (node weights)
-    // post-mix stage (electric-piano/src/main.rs:88-96): Tremolo on the summed bus -> Frame<2>
-    bool bus_tremolo = false;
+    // post-mix stage: one node on the summed bus.  Tremolo (electric-piano/src/main.rs:88-96) -> Frame<2>; Convolver
+    // (oscen-lib/src/convolution/mod.rs) -> as many channels as the voices
+    BusStage bus_stage = BusStage::None;
     HostFn tremolo_rate, tremolo_depth;
+    std::string bus_ir_name;                            // Convolver::with_ir(<name>()): the registered response ("": Convolver::new())
+    std::shared_ptr<const std::vector<float>> bus_ir;   // ... its taps as registered when the graph was lowered (null: the empty convolver)
     std::vector<UniformProg> uprogs;
     std::vector<int> release_slots; // release length in samples (ADSR_R_N) of every outer-rate envelope: sizes the reciprocal table
     int n_slots = 0;
@@ -237,6 +241,13 @@ struct UserFunction {
 };
 void register_user_function(const UserFunction& f); // throws on a malformed description
 bool unregister_user_function(const std::string& name);
+
+// impulse responses by name (`Convolver::with_ir(reverb_ir())`): mono, at the session rate; a registration under a name
+// that exists replaces it.  lookup: the call's path as written or its last segment, parentheses and arguments ignored.
+void register_ir(const std::string& name, const float* taps, size_t n_taps);
+bool unregister_ir(const std::string& name);
+std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved = nullptr);
+constexpr size_t MAX_IR_TAPS = (size_t)1 << 20; // (og_bus_conv.hip.h: OG_CONV_MAX_TAPS)
 
 // graph types usable as nodes of other graphs (nested graphs: `sub = SubGraph::new()`), expanded inline
 void register_graph_type(const std::string& name, const GraphDesc& g);
