@@ -525,6 +525,7 @@ struct Codegen {
         std::set<int> users; // consuming stages
     };
     std::vector<XVal> xvals;
+    bool uses_adsrp = false;     // some envelope has moving parameters: the unit includes og_adsr_params.hip.h
     bool dynamic_events = false; // some node receives events from another node: they arrive unannounced, so the
                                  // chunk variants that rely on "nothing happens in this chunk" and the pipelines are off
     std::ostringstream frame_end; // end of every frame: clear_event_outputs()
@@ -1226,10 +1227,41 @@ uint32_t adsr_samples(float t, float sr)
 }
 float adsr_coeff(uint32_t n) { return 1.0f - expf(-ADSR_CURVE_K / (float)n); }
 
+// attack / decay / sustain / release that are not block-uniform -- a ramped input, a per-voice input, a node output, an
+// expression of one: every lane derives the envelope's cached fields itself (og::AdsrP, og_adsr_params.hip.h).  No uniform
+// slots, no release table, no chunk specialisation: the body is the same in every chunk variant and kernel shape.
+void emit_adsr_params(NodeCtx& x, const Val& a, const Val& d, const Val& s, const Val& r)
+{
+    if (x.cg.out.lpv > 1)
+        fail_unsupported("node '" + x.n.decl->name + "': attack, decay, sustain and release of an envelope in an array-valued "
+                         "([f32; 32]) voice must be block-uniform values (constants or non-ramped broadcast inputs) in this version");
+    x.cg.uses_adsrp = true;
+    const std::string E = x.p + "e", SR = x.sf(x.sr_slot());
+    int w_stage = x.cg.new_state(x.n.decl->name + ".stage", false, [](const UEnv&) { return 0u; });
+    int w_rem = x.cg.new_state(x.n.decl->name + ".samples_remaining", false, [](const UEnv&) { return 0u; });
+    int w_level = x.cg.new_state(x.n.decl->name + ".level", true, [](const UEnv&) { return fbits(0.0f); });
+    int w_vel = x.cg.new_state(x.n.decl->name + ".velocity", true, [](const UEnv&) { return fbits(1.0f); });
+    // A gate event is queued (og::adsrp_push) and handled by the tick of its frame, which knows that frame's parameter
+    // values whatever their source -- the reference's order at the outer rate: it writes a node's value inputs, then runs
+    // its process_event_inputs() and its process() (codegen/emit_frame.rs:219-229).  The nodes of the oversampled region
+    // run their handlers in front of the inner loop (step 6a) and are written inside it (step 6): og::adsrp_tick<true>.
+    x.cg.S().decl << "    og::AdsrP " << E << ";\n";
+    x.cg.S().load << "        og::adsrp_load(" << E << ", og::ld_u(A, c, " << w_stage << "), og::ld_u(A, c, " << w_rem << "), og::ld_f(A, c, " << w_level
+                  << "), og::ld_f(A, c, " << w_vel << "));\n";
+    x.cg.S().store << "        og::st_u(A, c, " << w_stage << ", " << E << ".stage);\n"
+                   << "        og::st_u(A, c, " << w_rem << ", og::adsrp_rem(" << E << "));\n"
+                   << "        og::st_f(A, c, " << w_level << ", " << E << ".lv);\n"
+                   << "        og::st_f(A, c, " << w_vel << ", " << E << ".vel);\n";
+    x.on_event("gate", [&](const std::string& val) { return "                og::adsrp_push(" + E + ", " + val + ");\n"; });
+    x.set_out("output", std::string("og::adsrp_tick<") + (x.n.domain == 1 ? "true" : "false") + ">(" + E + ", " + a.e + ", " + d.e + ", " + s.e + ", " +
+                            r.e + ", " + SR + ")");
+}
+
 void emit_adsr(NodeCtx& x)
 {
-    Val a = x.in_uniform("attack"), d = x.in_uniform("decay"), s = x.in_uniform("sustain"),
-        r = x.in_uniform("release");
+    Val a = x.in("attack"), d = x.in("decay"), s = x.in("sustain"), r = x.in("release");
+    auto uniform = [](const Val& v) { return v.rate <= Rate::UBlock && (bool)v.host; };
+    if (!(uniform(a) && uniform(d) && uniform(s) && uniform(r))) return emit_adsr_params(x, a, d, s, r);
     const float k = x.rate_sr_factor();
     HostFn ha = a.host, hd = d.host, hs = s.host, hr = r.host;
     int s_an = x.slot_u([ha, k](const UEnv& e) { return adsr_samples(ha(e), e.sample_rate * k); });
@@ -5116,7 +5148,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             wide_args = std::to_string(xch) + ", " + std::to_string(fd);
     }
     out.hash = fnv1a(body_s + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
-                     "|wide" + wide_args + "|rt" + OG_RT_DIGEST);
+                     "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()));
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
 
@@ -5139,7 +5171,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     std::ostringstream pre;
     if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
     if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
-    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n\n"
+    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "") << "\n"
         << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
         << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
         << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"
