@@ -216,3 +216,18 @@ extern "C" {
     pub fn og_cluster_schedule_voice_events(c: *mut og_cluster, input: u32, n: u64, voices: *const u64,
                                             abs_frames: *const u64, values: *const c_float) -> c_int;
 }
+
+// ---- SamplePlayer: sample registry, the engine's device pool, publishing ----
+pub const OG_SAMPLE_NONE: u32 = 0xFFFF_FFFF;
+extern "C" {
+    pub fn og_register_sample(name: *const c_char, interleaved: *const c_float, frames: u64, channels: u32) -> c_int;
+    pub fn og_unregister_sample(name: *const c_char) -> c_int;
+    pub fn og_load_sample(e: *mut og_engine, name: *const c_char, index: *mut u32) -> c_int;
+    pub fn og_set_sample(e: *mut og_engine, node: *const c_char, index: u32) -> c_int;
+    pub fn og_set_voice_samples(e: *mut og_engine, node: *const c_char, first_voice: u32, count: u32,
+                                indices: *const u32) -> c_int;
+    pub fn og_cluster_load_sample(c: *mut og_cluster, name: *const c_char, index: *mut u32) -> c_int;
+    pub fn og_cluster_set_sample(c: *mut og_cluster, node: *const c_char, index: u32) -> c_int;
+    pub fn og_cluster_set_voice_samples(c: *mut og_cluster, node: *const c_char, first_voice: u64, count: u64,
+                                        indices: *const u32) -> c_int;
+}

@@ -247,6 +247,37 @@ int og_get_value(const og_engine* e, uint32_t input, float* out);
 int og_ramp_state(const og_engine* e, uint32_t input, float* current, float* target, uint32_t* frames_remaining);
 uint32_t og_active_ramps(const og_engine* e);
 
+/* ---- SamplePlayer (oscen-lib/src/sample_player/mod.rs): looping playback from the engine's device sample pool ------------
+ * `player = SamplePlayer::new()` (f32) / `SamplePlayer::<Frame<N>>::new()` (N = 2..4) inside the voice graph, at most 4 per
+ * graph; per frame it emits buf[playhead], then playhead += 1 and back to 0 once it reaches the length; no buffer or an empty
+ * one: exactly 0.0 on every channel.  Every VOICE holds its own buffer choice and playhead (state fields `<node>.sample`,
+ * `<node>.playhead` of og_read_state_field).  The reference binds the buffer through `external sample: AudioAsset;` and
+ * `graph.sample.load_wav(path)`; here (the text front end refuses `external`) it is bound by name through the calls below:
+ * register (decoding and rate conversion stay with the caller: samples are given at the graph's rate), load, set.
+ * Refused with OG_E_UNSUPPORTED: a player in an array-valued voice, in a node array, in a nested graph type, oversampled.
+ *
+ * Registry (process-wide, beside the impulse responses): interleaved frames, copied; channels 1..8; frames == 0 is legal
+ * (silence); frames * channels at most OG_MAX_SAMPLE_FLOATS = 2^28 (1 GiB); a name that exists is replaced (engines that
+ * loaded the old data keep their copy). */
+#define OG_SAMPLE_NONE 0xFFFFFFFFu       /* the unloaded state every player starts in (and og_init returns to) */
+#define OG_MAX_SAMPLE_CHANNELS 8u
+#define OG_MAX_SAMPLE_FLOATS (1u << 28)
+int og_register_sample(const char* name, const float* interleaved, uint64_t frames, uint32_t channels);
+int og_unregister_sample(const char* name);
+/* Brings a registered sample onto the engine's device, once per width the graph's players have, with the channel mapping of
+ * SamplePlayerConsumer::build (a 1-channel source broadcasts; otherwise player channel c takes source channel
+ * min(c, channels - 1): a mono player takes channel 0, not a downmix), and hands out a stable engine-local index; loading a
+ * name again returns the index it has.  Launches what is queued and waits for the device: not for the audio thread.  The
+ * pool holds up to 2^32 floats (OG_E_NOMEM past that).  Samples stay loaded across og_init. */
+int og_load_sample(og_engine* e, const char* name, uint32_t* index);
+/* Publishing: the voice plays sample `index` (or OG_SAMPLE_NONE) from its first frame, starting at the first frame of the
+ * first block processed after the call returns.  Publishing the index a voice already plays resets its playhead as well
+ * (a block-granular retrigger).  Blocks already queued (og_process_blocks_async, og_set_bus_batching) are not touched: the
+ * call launches them and orders itself behind them.  `node` is the player's name as og_read_state_field paths spell it;
+ * voices are the caller's numbers (og_group_voices).  og_set_sample publishes to every voice. */
+int og_set_sample(og_engine* e, const char* node, uint32_t index);
+int og_set_voice_samples(og_engine* e, const char* node, uint32_t first_voice, uint32_t count, const uint32_t* indices);
+
 /* Per-voice value input (the `voice_handlers.frequency -> voices.frequency`
  * edge, examples/fm-synth/src/lib.rs:88): takes effect at the next block. */
 int og_set_voice_value(og_engine* e, uint32_t input, uint32_t voice, float v);
@@ -494,6 +525,11 @@ int og_cluster_set_value(og_cluster* c, uint32_t input, float v);
 int og_cluster_set_value_ramp(og_cluster* c, uint32_t input, float v, uint32_t frames);
 int og_cluster_set_value_immediate(og_cluster* c, uint32_t input, float v);
 int og_cluster_set_voice_values(og_cluster* c, uint32_t input, uint64_t first_voice, uint64_t count, const float* v);
+/* SamplePlayer over a cluster: every shard loads the sample (the same index on all of them), og_cluster_set_sample goes to
+ * every shard, the voice range of og_cluster_set_voice_samples is split over the shards by global voice number */
+int og_cluster_load_sample(og_cluster* c, const char* name, uint32_t* index);
+int og_cluster_set_sample(og_cluster* c, const char* node, uint32_t index);
+int og_cluster_set_voice_samples(og_cluster* c, const char* node, uint64_t first_voice, uint64_t count, const uint32_t* indices);
 int og_cluster_push_voice_event(og_cluster* c, uint32_t input, uint64_t voice, uint32_t frame_offset, float scalar);
 int og_cluster_push_voice_value(og_cluster* c, uint32_t input, uint64_t voice, uint32_t frame_offset, float v);
 int og_cluster_schedule_voice_events(og_cluster* c, uint32_t input, uint64_t n, const uint64_t* voices,

@@ -719,6 +719,38 @@ int og_cluster_set_voice_values(og_cluster* c, uint32_t input, uint64_t first_vo
     });
 }
 
+int og_cluster_load_sample(og_cluster* c, const char* name, uint32_t* index)
+{
+    return ogabi::guard([&]() -> int {
+    if (!c || !name || !index) return set_err(OG_E_INVALID, "null argument");
+    for (size_t s = 0; s < c->shard.size(); ++s) { // (shards load the same names in the same order: one index for all)
+        uint32_t i = 0;
+        const int rc = og_load_sample(c->shard[s], name, &i);
+        if (rc != OG_OK) return rc;
+        if (s && i != *index) return set_err(OG_E_STATE, "og_cluster_load_sample: the shards disagree on the index (a shard was loaded on its own)");
+        *index = i;
+    }
+    return OG_OK;
+    });
+}
+
+int og_cluster_set_sample(og_cluster* c, const char* node, uint32_t index) { OG_CLUSTER_BROADCAST(og_set_sample(e, node, index)) }
+
+int og_cluster_set_voice_samples(og_cluster* c, const char* node, uint64_t first_voice, uint64_t count, const uint32_t* indices)
+{
+    return ogabi::guard([&]() -> int {
+    if (!c || !node || (count && !indices)) return set_err(OG_E_INVALID, "null argument");
+    if (first_voice + count > c->total) return set_err(OG_E_INVALID, "voice range out of bounds");
+    for (size_t s = 0; s < c->shard.size(); ++s) {
+        const uint64_t a = std::max(first_voice, c->lo[s]), b = std::min(first_voice + count, c->lo[s + 1]);
+        if (a >= b) continue;
+        const int rc = og_set_voice_samples(c->shard[s], node, (uint32_t)(a - c->lo[s]), (uint32_t)(b - a), indices + (a - first_voice));
+        if (rc != OG_OK) return rc;
+    }
+    return OG_OK;
+    });
+}
+
 int og_cluster_push_voice_event(og_cluster* c, uint32_t input, uint64_t voice, uint32_t frame_offset, float scalar)
 {
     if (!c) return set_err(OG_E_INVALID, "null cluster");

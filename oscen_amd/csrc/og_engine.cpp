@@ -15,7 +15,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -368,6 +370,42 @@ struct og_graph_desc {
     ogc::GraphDesc g;
 };
 
+// ---- samples by name (og_register_sample): process-wide, beside the impulse responses --------------------------------
+// interleaved frames as registered, at the graph's rate; a name that exists is replaced (engines that loaded the old
+// one keep their device copy)
+namespace {
+struct SampleData {
+    std::vector<float> interleaved;
+    uint32_t frames = 0, channels = 1;
+};
+std::map<std::string, std::shared_ptr<const SampleData>>& sample_registry()
+{
+    static std::map<std::string, std::shared_ptr<const SampleData>> R;
+    return R;
+}
+std::mutex& sample_registry_lock()
+{
+    static std::mutex m;
+    return m;
+}
+std::shared_ptr<const SampleData> lookup_sample(const std::string& name)
+{
+    std::lock_guard<std::mutex> lk(sample_registry_lock());
+    auto it = sample_registry().find(name);
+    return it == sample_registry().end() ? nullptr : it->second;
+}
+// SamplePlayerConsumer::build (sample_player/mod.rs:38-50): the source's channels onto a player of `width` channels,
+// frame-major -- one source channel broadcasts, otherwise target channel c takes source channel min(c, src_ch - 1)
+void map_sample_channels(const SampleData& s, uint32_t width, float* dst)
+{
+    for (size_t t = 0; t < s.frames; ++t)
+        for (uint32_t c = 0; c < width; ++c) {
+            const uint32_t sc = s.channels == 1 ? 0u : std::min(c, s.channels - 1u);
+            dst[t * width + c] = s.interleaved[t * s.channels + sc];
+        }
+}
+} // namespace
+
 // OSCEN_GPU_HOST_PROF=1: wall time of the host-side phases of the live path, printed when the engine is destroyed
 struct HostProf {
     enum { SYNC_EVENTS, INCREMENTAL, REBUILD, LAUNCH, RAMPS, EV_WAIT, EV_COMMIT, N };
@@ -529,6 +567,97 @@ struct og_engine {
         conv_retire(conv.old);
         conv.cur_from = conv.old_from = conv.fade_start = 0;
         q_conv.clear();
+    }
+    // ---- SamplePlayer: the device sample pool ------------------------------------------------------------------------
+    // og_load_sample appends a sample to the pool once per width the graph's players have (the reference's Vec<F>,
+    // frame-major) and gives it the next index; the descriptor table [player][sample_cap]{offset in floats, frames} is what
+    // the kernels read once per launch.  Growing either waits for the stream (not an audio-thread call).  Publishing
+    // (og_set_sample / og_set_voice_samples) writes the players' two state words behind the queued blocks.
+    struct LoadedSample {
+        std::string name;
+        uint32_t frames = 0, channels = 0; // the source's shape (snapshots check it)
+        uint32_t off[5] = {0, 0, 0, 0, 0}; // [width]: offset of the width's copy in the pool, in floats
+    };
+    std::vector<LoadedSample> samples;
+    float* d_pool = nullptr;
+    size_t pool_used = 0, pool_cap = 0; // floats
+    uint32_t* d_desc = nullptr;
+    uint32_t sample_cap = 0; // entries per player in d_desc
+    void pool_reserve(size_t need)
+    {
+        if (need <= pool_cap) return;
+        const size_t cap = std::max(need, std::max<size_t>(2 * pool_cap, (size_t)1 << 16));
+        float* n = nullptr;
+        HIPCK(hipMalloc(&n, cap * 4));
+        if (pool_used) HIPCK(hipMemcpyAsync(n, d_pool, pool_used * 4, hipMemcpyDeviceToDevice, stream));
+        HIPCK(hipStreamSynchronize(stream));
+        if (d_pool) HIPCK(hipFree(d_pool));
+        d_pool = n;
+        pool_cap = cap;
+    }
+    void upload_desc() // the whole table: a few words per sample
+    {
+        const size_t np = cg->players.size();
+        if (samples.size() > sample_cap) {
+            const uint32_t cap = std::max<uint32_t>(16u, 2u * (uint32_t)samples.size());
+            if (d_desc) HIPCK(hipFree(d_desc));
+            d_desc = nullptr;
+            sample_cap = 0;
+            HIPCK(hipMalloc(&d_desc, np * cap * 2 * 4));
+            sample_cap = cap;
+        }
+        std::vector<uint32_t> tab(np * sample_cap * 2, 0u);
+        for (size_t k = 0; k < np; ++k)
+            for (size_t i = 0; i < samples.size(); ++i) {
+                tab[2 * (k * sample_cap + i)] = samples[i].off[cg->players[k].channels];
+                tab[2 * (k * sample_cap + i) + 1] = samples[i].frames;
+            }
+        bounce.h2d(d_desc, tab.data(), tab.size() * 4, stream);
+        HIPCK(hipStreamSynchronize(stream));
+    }
+    // brings a registered sample onto the device (every width the players have); returns its index
+    uint32_t load_sample(const std::string& name, const SampleData& sd)
+    {
+        flush_bus();
+        HIPCK(hipStreamSynchronize(stream)); // (launches in flight read the pool and the table)
+        LoadedSample ls;
+        ls.name = name;
+        ls.frames = sd.frames;
+        ls.channels = sd.channels;
+        bool widths[5] = {false, false, false, false, false};
+        size_t need = pool_used;
+        for (const auto& pl : cg->players)
+            if (!widths[pl.channels]) {
+                widths[pl.channels] = true;
+                need += (size_t)sd.frames * pl.channels;
+            }
+        if (need >= ((size_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
+        pool_reserve(need);
+        std::vector<float> mapped;
+        for (uint32_t w = 1; w <= 4; ++w) {
+            if (!widths[w]) continue;
+            ls.off[w] = (uint32_t)pool_used;
+            mapped.resize((size_t)sd.frames * w);
+            map_sample_channels(sd, w, mapped.data());
+            if (!mapped.empty()) bounce.h2d(d_pool + pool_used, mapped.data(), mapped.size() * 4, stream);
+            HIPCK(hipStreamSynchronize(stream));
+            pool_used += mapped.size();
+        }
+        samples.push_back(ls);
+        upload_desc();
+        return (uint32_t)samples.size() - 1;
+    }
+    int find_player(const char* node) const
+    {
+        std::string p; // the spelling of og_read_state_field paths: `inner.player` -> `inner_player`
+        for (const char* c = node; *c; ++c) {
+            if (*c == '[') p += "__";
+            else if (*c == '.') p.push_back('_');
+            else if (*c != ']' && !isspace((unsigned char)*c)) p.push_back(*c);
+        }
+        for (size_t k = 0; k < cg->players.size(); ++k)
+            if (cg->players[k].name == p) return (int)k;
+        return -1;
     }
     OgEvent* d_events = nullptr;
     size_t ev_cap = 0;
@@ -818,6 +947,8 @@ struct og_engine {
         (void)hipFree(d_partials);
         (void)hipFree(d_partials2);
         (void)hipFree(d_rcp);
+        (void)hipFree(d_pool);
+        (void)hipFree(d_desc);
         for (float* p : rcp_old) (void)hipFree(p);
         (void)hipFree(d_stage_bus);
         (void)hipFree(d_bus);
@@ -1543,6 +1674,14 @@ struct og_engine {
             e.block_starts = starts;
             e.n_blocks = nb;
             for (const auto& up : cg->uprogs) A.slots[up.dst] = up.fn(e);
+        }
+        if (cg->player_slot0 >= 0) { // SamplePlayer: the pool and the descriptor table (og_sample_player.hip.h)
+            uint32_t* ps = A.slots + cg->player_slot0;
+            ps[0] = (uint32_t)((uintptr_t)d_pool & 0xFFFFFFFFu);
+            ps[1] = (uint32_t)((uint64_t)(uintptr_t)d_pool >> 32);
+            ps[2] = (uint32_t)((uintptr_t)d_desc & 0xFFFFFFFFu);
+            ps[3] = (uint32_t)((uint64_t)(uintptr_t)d_desc >> 32);
+            ps[4] = sample_cap;
         }
         if (rcp_cover(release_need(A.slots))) {
             A.rcp_tab = d_rcp;
@@ -2453,6 +2592,98 @@ int og_set_voice_value(og_engine* e, uint32_t input, uint32_t voice, float v)
     return og_set_voice_values(e, input, voice, 1, &v);
 }
 
+// ---- SamplePlayer: registry, device pool, publishing ------------------------------------------------------------------
+int og_register_sample(const char* name, const float* interleaved, uint64_t frames, uint32_t channels)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name || !*name) return set_err(OG_E_INVALID, "og_register_sample: a sample needs a name");
+    if (channels < 1 || channels > OG_MAX_SAMPLE_CHANNELS)
+        return set_err(OG_E_INVALID, "og_register_sample: 1 to " + std::to_string(OG_MAX_SAMPLE_CHANNELS) + " channels");
+    if (frames > OG_MAX_SAMPLE_FLOATS / channels)
+        return set_err(OG_E_INVALID, "og_register_sample: '" + std::string(name) + "' has more than 2^28 samples (frames x channels)");
+    if (frames && !interleaved) return set_err(OG_E_INVALID, "null argument");
+    auto sd = std::make_shared<SampleData>();
+    sd->frames = (uint32_t)frames;
+    sd->channels = channels;
+    if (frames) sd->interleaved.assign(interleaved, interleaved + (size_t)frames * channels);
+    std::lock_guard<std::mutex> lk(sample_registry_lock());
+    sample_registry()[name] = sd;
+    return OG_OK;
+    });
+}
+
+int og_unregister_sample(const char* name)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name) return set_err(OG_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(sample_registry_lock());
+    return sample_registry().erase(name) ? OG_OK : set_err(OG_E_INVALID, std::string("no sample '") + name + "'");
+    });
+}
+
+int og_load_sample(og_engine* e, const char* name, uint32_t* index)
+{
+    if (!e || !name || !index) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        if (e->cg->players.empty()) return set_err(OG_E_INVALID, "og_load_sample: this graph has no SamplePlayer");
+        for (size_t i = 0; i < e->samples.size(); ++i)
+            if (e->samples[i].name == name) { // idempotent per name
+                *index = (uint32_t)i;
+                return OG_OK;
+            }
+        const auto sd = lookup_sample(name);
+        if (!sd) return set_err(OG_E_INVALID, std::string("unknown sample '") + name + "'; samples are registered with og_register_sample");
+        HIPCK(hipSetDevice(e->device));
+        *index = e->load_sample(name, *sd);
+        return OG_OK;
+    });
+}
+
+int og_set_voice_samples(og_engine* e, const char* node, uint32_t first, uint32_t count, const uint32_t* indices)
+{
+    if (!e || !node || (count && !indices)) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        const int k = e->find_player(node);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no SamplePlayer named '") + node + "'");
+        if ((uint64_t)first + count > e->V) return set_err(OG_E_INVALID, "voice range out of bounds");
+        for (uint32_t i = 0; i < count; ++i)
+            if (indices[i] != OG_SAMPLE_NONE && indices[i] >= e->samples.size())
+                return set_err(OG_E_INVALID, "sample index " + std::to_string(indices[i]) + " was not handed out by og_load_sample");
+        if (!count) return OG_OK;
+        HIPCK(hipSetDevice(e->device));
+        e->flush_bus(); // queued blocks keep what they were queued under: the words are written behind them, in stream order
+        uint32_t* smp = e->d_state + (size_t)e->cg->players[k].sample_word * e->V;
+        uint32_t* ph = e->d_state + (size_t)e->cg->players[k].playhead_word * e->V;
+        if (e->phys_of.empty()) {
+            e->bounce.h2d(smp + first, indices, (size_t)count * 4, e->stream);
+            HIPCK(hipMemsetAsync(ph + first, 0, (size_t)count * 4, e->stream));
+        } else { // grouped voices: the range is scattered over the planes
+            std::vector<uint32_t> a(e->V), b(e->V);
+            if (count < e->V) {
+                e->bounce.d2h(a.data(), smp, (size_t)e->V * 4, e->stream);
+                e->bounce.d2h(b.data(), ph, (size_t)e->V * 4, e->stream);
+            }
+            for (uint32_t i = 0; i < count; ++i) {
+                a[e->phys_of[first + i]] = indices[i];
+                b[e->phys_of[first + i]] = 0u;
+            }
+            e->bounce.h2d(smp, a.data(), (size_t)e->V * 4, e->stream);
+            e->bounce.h2d(ph, b.data(), (size_t)e->V * 4, e->stream);
+        }
+        HIPCK(hipStreamSynchronize(e->stream));
+        return OG_OK;
+    });
+}
+
+int og_set_sample(og_engine* e, const char* node, uint32_t index)
+{
+    if (!e || !node) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        const std::vector<uint32_t> all(e->V, index);
+        return og_set_voice_samples(e, node, 0, e->V, all.data());
+    });
+}
+
 int og_push_voice_event(og_engine* e, uint32_t input, uint32_t voice, uint32_t frame_offset, float scalar)
 {
     if (!e) return set_err(OG_E_INVALID, "null engine");
@@ -3202,6 +3433,23 @@ size_t conv_bytes(const og_engine* e)
                                conv_hist_frames(e) * e->cg->voice_channels) * 4;
 }
 
+// SamplePlayer: a section of its own at the very end -- the loaded samples' names and shapes in index order (the per-voice
+// words are state planes like any other); og_load_state resolves the names through the registry and loads them
+struct SnapSamples {
+    uint32_t magic, n;
+};
+struct SnapSample {
+    uint32_t name_len, frames, channels, reserved;
+};
+constexpr uint32_t SNAP_SMP_MAGIC = 0x504D534Fu; // "OSMP"
+size_t samples_bytes(const og_engine* e)
+{
+    if (e->cg->players.empty()) return 0;
+    size_t n = sizeof(SnapSamples);
+    for (const auto& ls : e->samples) n += sizeof(SnapSample) + (ls.name.size() + 3) / 4 * 4;
+    return n;
+}
+
 size_t dsp_bytes(const og_engine* e)
 {
     return (e->cg->state.size() + e->cg->lane_state.size() * e->cg->lpv * e->cg->lane_width) * (size_t)e->V * 4 +
@@ -3244,7 +3492,7 @@ size_t og_state_bytes(const og_engine* e)
     if (!e) return 0;
     std::vector<SnapEvent> evs;
     collect_unconsumed(e, evs);
-    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e);
+    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e);
     });
 }
 
@@ -3256,7 +3504,7 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
         e->flush_bus(); // queued blocks consume their events first: what is collected below is what frame_now has not reached
         std::vector<SnapEvent> evs;
         collect_unconsumed(e, evs);
-        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e)) throw std::runtime_error("buffer too small");
+        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e)) throw std::runtime_error("buffer too small");
         const size_t a = e->cg->state.size() * (size_t)e->V * 4, b = e->cg->lane_state.size() * (size_t)e->V * e->cg->lpv * e->cg->lane_width * 4;
         e->bounce.d2h(dst, e->d_state, a, e->stream);
         if (b) e->bounce.d2h((char*)dst + a, e->d_lane_state, b, e->stream);
@@ -3295,6 +3543,21 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
             if (ko) memcpy(p, cv.old->taps.data(), (size_t)ko * 4);
             p += (size_t)ko * 4;
             if (hf) e->bounce.d2h(p, e->d_hist + (e->hist_pos - hf) * vc, hf * vc * 4, e->stream); // (hf <= hist_keep <= hist_pos)
+            p += hf * vc * 4;
+        }
+        if (!e->cg->players.empty()) {
+            const SnapSamples sh{SNAP_SMP_MAGIC, (uint32_t)e->samples.size()};
+            memcpy(p, &sh, sizeof sh);
+            p += sizeof sh;
+            for (const auto& ls : e->samples) {
+                const SnapSample ss{(uint32_t)ls.name.size(), ls.frames, ls.channels, 0u};
+                memcpy(p, &ss, sizeof ss);
+                p += sizeof ss;
+                const size_t padded = (ls.name.size() + 3) / 4 * 4;
+                memset(p, 0, padded);
+                memcpy(p, ls.name.data(), ls.name.size());
+                p += padded;
+            }
         }
         return OG_OK;
     });
@@ -3314,8 +3577,64 @@ int og_load_state(og_engine* e, const void* src, size_t len)
     if (h.magic != SNAP_MAGIC || (h.version != 2u && h.version != 3u) || h.n_inputs != e->cg->inputs.size() || len < dsp + fixed ||
         h.n_events > (uint64_t)((len - dsp - fixed) / sizeof(SnapEvent)) || len < dsp + control_bytes(e, (size_t)h.n_events, grouped))
         return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
-    const size_t full_len = len;
+    size_t full_len = len;
     len = dsp + control_bytes(e, (size_t)h.n_events, grouped); // what follows is the post-mix Convolver's section
+    // ... and, last, the SamplePlayer section: found from the front (behind the Convolver's, whose size its header gives)
+    struct WantSample {
+        std::string name;
+        uint32_t frames, channels;
+    };
+    std::vector<WantSample> want_samples;
+    if (!e->cg->players.empty()) {
+        const int rc = ogabi::guard([&]() -> int {
+            size_t at = len;
+            if (e->conv_on()) {
+                SnapConv pc{};
+                if (full_len - at < sizeof pc) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
+                memcpy(&pc, (const char*)src + at, sizeof pc);
+                const uint64_t ko = pc.k_old == 0xFFFFFFFFu ? 0u : pc.k_old;
+                const uint64_t n = sizeof pc + ((uint64_t)pc.k_cur + ko + (uint64_t)pc.hist_frames * pc.channels) * 4;
+                if (n > full_len - at) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
+                at += (size_t)n;
+            }
+            const size_t smp_at = at;
+            SnapSamples sh{};
+            bool ok = full_len - at >= sizeof sh;
+            if (ok) memcpy(&sh, (const char*)src + at, sizeof sh);
+            ok = ok && sh.magic == SNAP_SMP_MAGIC;
+            at += sizeof sh;
+            for (uint32_t i = 0; ok && i < sh.n; ++i) {
+                SnapSample ss{};
+                ok = full_len - at >= sizeof ss;
+                if (!ok) break;
+                memcpy(&ss, (const char*)src + at, sizeof ss);
+                at += sizeof ss;
+                const size_t padded = ((size_t)ss.name_len + 3) / 4 * 4;
+                ok = ss.name_len <= 4096u && full_len - at >= padded;
+                if (!ok) break;
+                want_samples.push_back({std::string((const char*)src + at, ss.name_len), ss.frames, ss.channels});
+                at += padded;
+            }
+            if (!ok || at != full_len) return set_err(OG_E_INVALID, "state blob: the SamplePlayer section is missing or malformed");
+            // every sample must be there, in the shape it was saved with, before anything is changed
+            for (size_t i = 0; i < want_samples.size(); ++i) {
+                const WantSample& w = want_samples[i];
+                if (i < e->samples.size()) {
+                    const auto& ls = e->samples[i];
+                    if (ls.name != w.name || ls.frames != w.frames || ls.channels != w.channels)
+                        return set_err(OG_E_INVALID, "state blob: sample " + std::to_string(i) + " is '" + w.name + "', this engine has loaded '" + ls.name + "' there");
+                    continue;
+                }
+                const auto sd = lookup_sample(w.name);
+                if (!sd) return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is not registered (og_register_sample)");
+                if (sd->frames != w.frames || sd->channels != w.channels)
+                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is registered with another shape than the one it was saved with");
+            }
+            full_len = smp_at;
+            return OG_OK;
+        });
+        if (rc != OG_OK) return rc;
+    }
     SnapConv sc{};
     if (e->conv_on()) {
         bool ok = full_len - len >= sizeof sc;
@@ -3369,6 +3688,12 @@ int og_load_state(og_engine* e, const void* src, size_t len)
         }
         e->reset_timeline();
         HIPCK(hipStreamSynchronize(e->stream));
+        for (size_t i = e->samples.size(); i < want_samples.size(); ++i) { // (validated above; the registry may have changed since)
+            const auto sd = lookup_sample(want_samples[i].name);
+            if (!sd || sd->frames != want_samples[i].frames || sd->channels != want_samples[i].channels)
+                throw ogabi::Error(OG_E_INVALID, "state blob: sample '" + want_samples[i].name + "' is not registered in the shape it was saved with");
+            (void)e->load_sample(want_samples[i].name, *sd);
+        }
         if (e->conv_on()) {
             const size_t vc = e->cg->voice_channels;
             const size_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old;

@@ -436,6 +436,7 @@ int node_weight(const std::string& type)
     if (type.rfind("IirLowpass", 0) == 0) return 14;
     if (type.rfind("LP18Filter", 0) == 0) return 40;
     if (type.rfind("Delay", 0) == 0) return 30;
+    if (type.rfind("SamplePlayer", 0) == 0) return 4;
     if (type.rfind("Crossfade", 0) == 0) return 2;
     if (type.rfind("HardClip", 0) == 0) return 2;
     const int uw = user_weight(type);
@@ -1597,6 +1598,41 @@ void emit_delay(NodeCtx& x)
                             dsv + ", " + fbv + ", " + wp + ", " + fc + ", " + pre + ", ring_lds[" + K + "], c.lane, f - cbase)");
 }
 
+// SamplePlayer (oscen-lib/src/sample_player/mod.rs): the buffer is a span of the engine's device sample pool, chosen per voice
+// (state word `sample`, an engine-local index; OG_SAMPLE_NONE until published) and read a chunk ahead (og_sample_player.hip.h)
+void emit_sample_player(NodeCtx& x)
+{
+    const int C = std::max(1, x.n.type->variant);
+    const std::string nm = x.n.decl->name;
+    if (x.cg.out.lpv > 1)
+        fail_unsupported("node '" + nm + "': a SamplePlayer inside an array-valued voice ([f32; 32] nodes) is not supported in this version");
+    if (x.n.domain == 1 || x.n.decl->rate_factor != 1)
+        fail_unsupported("node '" + nm + "': a SamplePlayer in an oversampled (`* N`) domain is not supported in this version");
+    if (x.cg.out.players.size() >= MAX_PLAYERS) fail("at most " + std::to_string(MAX_PLAYERS) + " SamplePlayer nodes per graph");
+    const int k = (int)x.cg.out.players.size();
+    if (x.cg.out.player_slot0 < 0) { // filled by the engine per launch: pool address, table address, entries per player
+        x.cg.out.player_slot0 = x.cg.new_slot([](const UEnv&) { return 0u; });
+        for (int i = 1; i < 5; ++i) (void)x.cg.new_slot([](const UEnv&) { return 0u; });
+    }
+    const std::string smp = x.state_u("sample", 0xFFFFFFFFu), ph = x.state_u("playhead", 0);
+    const int w_ph = (int)x.cg.out.state.size() - 1;
+    x.cg.out.players.push_back({nm, C, w_ph - 1, w_ph});
+    const std::string P = x.p + "pl", T = "<" + std::to_string(C) + ">";
+    x.cg.S().decl << "    og::Player" << T << " " << P << ";\n";
+    x.cg.S().pre << "    og::player_begin" << T << "(A, " << x.cg.out.player_slot0 << ", " << k << "u, c.valid, " << smp << ", " << ph << ", " << P << ");\n";
+    x.cg.S().chunk_begin << "        og::player_chunk_begin" << T << "(" << P << ", " << ph << ", base + OG_BUS_CHUNK < A.frames);\n";
+    const std::string fr = x.p + "frame";
+    x.cg.os() << "        const og::Frame" << T << " " << fr << " = og::player_tick" << T << "(" << P << ", " << ph << ");\n";
+    if (C == 1) {
+        x.set_out("output", fr + ".v[0]");
+        return;
+    }
+    std::vector<std::string> outs;
+    for (int c = 0; c < C; ++c) outs.push_back(fr + ".v[" + std::to_string(c) + "]");
+    x.set_out_frame("output", outs);
+}
+bool is_sample_player(const std::string& type) { return normalize_type(type).rfind("SamplePlayer", 0) == 0; }
+
 // (inputs are resolved in separate statements: operand evaluation order is unspecified in C++ and
 //  resolving an input can allocate cut-crossing channels, whose numbering must be deterministic)
 void emit_binary(NodeCtx& x, const char* a, const char* b, const char* op)
@@ -1802,6 +1838,13 @@ const std::map<std::string, NodeTypeInfo>& registry()
                                 {"output"}, emit_lp18, 0, 2};
         r["Delay::new"] = {{{"input", S, 0, -1}, {"delay_samples", V, 0, 0}, {"feedback", V, 0, 1}}, {"output"}, emit_delay, 0, 2};
         r["HardClip::new"] = {{{"input", S, 0, -1}}, {"output"}, emit_hardclip, 0, 0};
+        r["SamplePlayer::new"] = {{}, {"output"}, emit_sample_player, 1, 0};
+        for (int w : {2, 3, 4}) { // SamplePlayer::<Frame<N>>::new
+            NodeTypeInfo t = r["SamplePlayer::new"];
+            t.variant = w;
+            t.out_channels = {w};
+            r["SamplePlayer<" + std::to_string(w) + ">::new"] = t;
+        }
         r["AmplitudeSource::new"] = {{{"frequency", V, 440.0f, -1}, {"gate", E, 0, -1}, {"brightness", V, 30.0f, -1},
                                       {"velocity_scaling", V, 50.0f, -1}, {"decay_rate", V, 90.0f, -1},
                                       {"harmonic_decay", V, 70.0f, -1}, {"key_scaling", V, 50.0f, -1},
@@ -2195,6 +2238,9 @@ GraphDesc expand_arrays(const GraphDesc& g)
                      n.name.substr(0, us) + "')");
         }
     }
+    for (const GNode& n : g.nodes)
+        if (n.array_len && is_sample_player(n.type))
+            fail_unsupported("node '" + n.name + "': a SamplePlayer in a node array is not supported in this version");
     if (arr.empty()) return g;
     GraphDesc o;
     o.name = g.name;
@@ -2334,6 +2380,9 @@ GraphDesc expand_nested(const GraphDesc& g, int depth)
         const GraphDesc* t = type_of(n);
         if (!t) continue;
         subs[n.name].g = expand_nested(expand_arrays(*t), depth + 1);
+        for (const GNode& in : subs[n.name].g.nodes)
+            if (is_sample_player(in.type) && !n.inline_bare)
+                fail_unsupported("node '" + n.name + "': a SamplePlayer ('" + in.name + "') in a nested graph type is not supported in this version");
         if (n.rate_factor != 1) { // `inner = InnerGraph::new() * 2`: every node of the nested graph runs at that rate
             for (GNode& in : subs[n.name].g.nodes) {
                 if (in.rate_factor != 1)
@@ -3779,6 +3828,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         const char* env_split = ogabi::experiment_knob("OGC_SPLIT");
         bool any_delay = false; // delay lines are staged per chunk by the ordinary kernel only
         for (int ni : order) any_delay = any_delay || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
+        for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
         // a Frame<2> voice output (two bus tiles) is summed by the ordinary kernel only
         std::function<int(const ExprP&)> width_of = [&](const ExprP& e) -> int {
             if (!e) return 1;
@@ -4260,6 +4310,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     if (unroll > 1) {
         if (out.lpv > 1) unroll = 2;
         else if (!out.rings.empty()) unroll = 4;
+        else if (!out.players.empty()) unroll = 16; // (a tick shifts the chunk's staged frames down: renames in a straight-line chunk)
         else if (cg.N > 1) unroll = 16;
         else unroll = (has_env && graph_weight >= 70) ? 4 : 8; // (fm_voice: sixteen is worth +0.7 % over four and brings spills into the tapped variants' chunk bodies)
     }
@@ -4366,7 +4417,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     body << events_code(all_stages, false);
     body << "    for (uint32_t base = 0; base < A.frames; base += OG_BUS_CHUNK) {\n"
          << "        const uint32_t n = min((uint32_t)OG_BUS_CHUNK, A.frames - base);\n"
-         << (out.rings.empty() ? std::string() : "        cbase = base;\n" + cat(all_stages, &Codegen::Sect::chunk_begin))
+         << (out.rings.empty() ? std::string() : std::string("        cbase = base;\n")) << cat(all_stages, &Codegen::Sect::chunk_begin)
          << "        if (n == OG_BUS_CHUNK && __all((int)(c.next_ev >= base + OG_BUS_CHUNK))) {\n"
          << "            // no lane of this wave has an event in the chunk: straight-line body\n";
     {
@@ -4393,7 +4444,7 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                          << ind << "if (!(base1 + OG_BUS_CHUNK <= A.frames && " << stay_path1 << (stay == "1" ? "" : " && " + stay) << ")) break;\n"
                          << ind << "og::bus_chunk_reduce(A, c, bus, base, OG_BUS_CHUNK);\n"
                          << ind << "base = base1;\n"
-                         << (out.rings.empty() ? std::string() : ind + "cbase = base;\n" + cat(all_stages, &Codegen::Sect::chunk_begin))
+                         << (out.rings.empty() ? std::string() : ind + "cbase = base;\n") << cat(all_stages, &Codegen::Sect::chunk_begin)
                          << ind1 << "}\n";
                 }
             };
@@ -5148,7 +5199,8 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             wide_args = std::to_string(xch) + ", " + std::to_string(fd);
     }
     out.hash = fnv1a(body_s + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
-                     "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()));
+                     "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()) +
+                     (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST));
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
 
@@ -5171,7 +5223,8 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     std::ostringstream pre;
     if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
     if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
-    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "") << "\n"
+    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "")
+        << (out.players.empty() ? "" : "#include \"og_sample_player.hip.h\"\n") << "\n"
         << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
         << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
         << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"
@@ -5231,6 +5284,11 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     // and is 3.3 % faster in an interleaved A/B (1.57e11 -> 1.62e11 at 262 144 voices): taken.  Four waves (128 VGPRs)
     // spill inside the frame loop.
     int waves_eu = (out.lpv > 1 && out.lane_width == 8) ? 3 : 4;
+    { // every player channel keeps two chunks of frames in registers (32 VGPRs): past two channels, two waves per SIMD
+        int player_channels = 0;
+        for (const auto& pl : out.players) player_channels += pl.channels;
+        if (player_channels > 2) waves_eu = 2;
+    }
     if (const char* ew = ogabi::experiment_knob("OGC_WAVES_EU")) waves_eu = std::max(1, std::min(8, atoi(ew)));
     // the zero variant: only next to the kernels that read no ramp table (`_00z`, `_01z`)
     auto zero_variants = [&](const std::function<void(std::ostringstream& zsrc, const char* z, const char* v, const char* taps)>& f) {

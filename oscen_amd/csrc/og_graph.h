@@ -144,6 +144,16 @@ struct CompiledGraph {
     std::vector<StateWord> state;      // per-voice words
     std::vector<StateWord> lane_state; // per-(voice, lane) words of LPV > 1 graphs
     std::vector<RingSpec> rings;       // delay lines (at most OG_MAX_RINGS)
+    // SamplePlayer nodes (og_sample_player.hip.h; at most MAX_PLAYERS): the engine publishes a sample by writing the two state
+    // words; player_slot0 is the first of five slots the ENGINE fills per launch (pool address, descriptor table address,
+    // entries per player) -- they have no UniformProg
+    struct PlayerSpec {
+        std::string name;
+        int channels = 1;                          // 1 = f32, N = Frame<N>
+        int sample_word = -1, playhead_word = -1;  // state planes
+    };
+    std::vector<PlayerSpec> players;
+    int player_slot0 = -1;
     int lpv = 1;                       // lanes per voice (8 for the electric-piano voice)
     int lane_width = 1;                // words a lane owns of every lane_state array (OG_HPL = 4 when lpv > 1)
     bool can_split = false;            // a two-wave pipeline variant of the kernel exists (og_k2_*)
@@ -248,6 +258,7 @@ void register_ir(const std::string& name, const float* taps, size_t n_taps);
 bool unregister_ir(const std::string& name);
 std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved = nullptr);
 constexpr size_t MAX_IR_TAPS = (size_t)1 << 20; // (og_bus_conv.hip.h: OG_CONV_MAX_TAPS)
+constexpr size_t MAX_PLAYERS = 4;                   // SamplePlayer nodes per graph
 
 // graph types usable as nodes of other graphs (nested graphs: `sub = SubGraph::new()`), expanded inline
 void register_graph_type(const std::string& name, const GraphDesc& g);
