@@ -472,7 +472,7 @@ struct Codegen {
     std::vector<char> emitted;                   // per node
 
     // Emitted code sections.  There are up to four sets: a graph may be cut into pipeline stages
-    // (see "pipeline stages" in compile()); nodes of stage s write into sec[s].  The ordinary
+    // (see Lowering::plan_pipeline_stages); nodes of stage s write into sec[s].  The ordinary
     // kernel simply concatenates the sets; the pipelined kernels give groups of them to separate waves.
     struct Sect {
         std::ostringstream decl, load, derive, pre, pre_store, store;
@@ -3068,39 +3068,34 @@ std::string drop_node_indices(const std::string& t)
     }
     return o;
 }
-} // namespace
 
-void check_reference_rules(const GraphDesc& g)
-{
+// The reference's endpoint kinds on the description AS WRITTEN (infer_endpoint_types, ir/lower.rs:233-338): typed graph inputs /
+// outputs, inline delays and stream-only policies seed them, connection statements propagate them both ways to a fixpoint.
+// (Lowering::infer_overwritten_edges has an inference of its own: after expansion, array elements canonicalised, a negation
+//  passes its operand's kind through.  This one runs before expansion and infers nothing through a negation.  They look alike
+//  and are deliberately not the same: not to be merged.)
+struct RefKinds {
     struct Named {
         int what; // 0 graph input, 1 graph output, 2 node
         uint32_t array_len = 0, rate = 1;
     };
+    struct Stmt {
+        std::string src_text, dst_text, policy;
+        ExprP src;
+        RefEndpoint src_ep, dst_ep; // src_ep.ok: the source is a plain endpoint
+    };
     std::map<std::string, Named> names;
     std::map<std::pair<std::string, std::string>, RK> kinds;
-    auto decl = [](Kind k) { return k == Kind::Stream ? RK::Stream : (k == Kind::Value ? RK::Value : RK::Event); };
-    for (const GInput& in : g.inputs) {
-        names[in.name] = {0, 0, 1};
-        kinds[{in.name, in.name}] = decl(in.kind);
-    }
-    for (const GOutput& o : g.outputs) {
-        names[o.name] = {1, 0, 1};
-        kinds[{o.name, o.name}] = decl(o.kind);
-    }
-    for (const GNode& n : g.nodes) {
-        if (n.bus) return; // (a lowered wrapper with its post-mix stage: checked when it was written as a wrapper)
-        names[n.name] = {2, n.array_len, n.rate_factor ? n.rate_factor : 1u};
-        if (n.name.rfind("__inline_delay_", 0) == 0) { // `-> [N] ->`: synth_delay_endpoints (ir/lower.rs:186-206)
-            kinds[{n.name, "input"}] = kinds[{n.name, "output"}] = RK::Stream;
-            kinds[{n.name, "delay_samples"}] = kinds[{n.name, "feedback"}] = RK::Value;
-        }
-    }
-    auto lookup = [&](const std::string& node, const std::string& ep) {
+    std::vector<Stmt> stmts;
+    bool lowered_wrapper = false; // a lowered wrapper with its post-mix stage: checked when it was written as a wrapper
+    RK lookup(const std::string& node, const std::string& ep) const
+    {
         auto it = kinds.find({node, ep});
         return it == kinds.end() ? RK::Unknown : it->second;
-    };
+    }
     // endpoint_kind_of (ir/lower.rs:937-959)
-    std::function<RK(const ExprP&)> kind_of = [&](const ExprP& e) -> RK {
+    RK kind_of(const ExprP& e) const
+    {
         if (!e) return RK::Unknown;
         switch (e->t) {
         case Expr::Num: return RK::Value;
@@ -3113,13 +3108,36 @@ void check_reference_rules(const GraphDesc& g)
         }
         default: return RK::Unknown; // calls, methods, negation: no inference
         }
-    };
-    struct Stmt {
-        std::string src_text, dst_text, policy;
-        ExprP src;
-        RefEndpoint src_ep, dst_ep; // src_ep.ok: the source is a plain endpoint
-    };
-    std::vector<Stmt> stmts;
+    }
+};
+
+RefKinds reference_endpoint_kinds(const GraphDesc& g)
+{
+    RefKinds rk;
+    auto& names = rk.names;
+    auto& kinds = rk.kinds;
+    auto& stmts = rk.stmts;
+    using Stmt = RefKinds::Stmt;
+    auto decl = [](Kind k) { return k == Kind::Stream ? RK::Stream : (k == Kind::Value ? RK::Value : RK::Event); };
+    for (const GInput& in : g.inputs) {
+        names[in.name] = {0, 0, 1};
+        kinds[{in.name, in.name}] = decl(in.kind);
+    }
+    for (const GOutput& o : g.outputs) {
+        names[o.name] = {1, 0, 1};
+        kinds[{o.name, o.name}] = decl(o.kind);
+    }
+    for (const GNode& n : g.nodes) {
+        if (n.bus) { // (a lowered wrapper with its post-mix stage: checked when it was written as a wrapper)
+            rk.lowered_wrapper = true;
+            return rk;
+        }
+        names[n.name] = {2, n.array_len, n.rate_factor ? n.rate_factor : 1u};
+        if (n.name.rfind("__inline_delay_", 0) == 0) { // `-> [N] ->`: synth_delay_endpoints (ir/lower.rs:186-206)
+            kinds[{n.name, "input"}] = kinds[{n.name, "output"}] = RK::Stream;
+            kinds[{n.name, "delay_samples"}] = kinds[{n.name, "feedback"}] = RK::Value;
+        }
+    }
     for (size_t i = 0; i < g.edges.size(); ++i) {
         const GEdge& e = g.edges[i];
         if (e.feedback) continue; // (second leg of `src -> [via] -> dst`: folded into its statement below)
@@ -3147,16 +3165,24 @@ void check_reference_rules(const GraphDesc& g)
     for (size_t round = 0; round <= stmts.size(); ++round) {
         bool changed = false;
         for (const Stmt& st : stmts) {
-            const RK sk = kind_of(st.src);
+            const RK sk = rk.kind_of(st.src);
             if (sk != RK::Unknown && kinds.emplace(std::make_pair(st.dst_ep.node, st.dst_ep.endpoint), sk).second) changed = true;
-            const RK dk = lookup(st.dst_ep.node, st.dst_ep.endpoint);
+            const RK dk = rk.lookup(st.dst_ep.node, st.dst_ep.endpoint);
             if (dk != RK::Unknown && st.src_ep.ok && kinds.emplace(std::make_pair(st.src_ep.node, st.src_ep.endpoint), dk).second) changed = true;
         }
         if (!changed) break;
     }
+    return rk;
+}
+} // namespace
+
+void check_reference_rules(const GraphDesc& g)
+{
+    RefKinds rk = reference_endpoint_kinds(g);
+    if (rk.lowered_wrapper) return;
     // (1) kind compatibility, statement by statement
-    for (const Stmt& st : stmts) {
-        const RK sk = kind_of(st.src), dk = lookup(st.dst_ep.node, st.dst_ep.endpoint);
+    for (const RefKinds::Stmt& st : rk.stmts) {
+        const RK sk = rk.kind_of(st.src), dk = rk.lookup(st.dst_ep.node, st.dst_ep.endpoint);
         if (sk == RK::Unknown || dk == RK::Unknown) continue;
         const bool ok = sk == dk || (sk == RK::Value && dk == RK::Stream);
         if (!ok)
@@ -3172,7 +3198,7 @@ void check_reference_rules(const GraphDesc& g)
     std::vector<std::string> bucket_order;
     for (const GEdge& e : g.edges) {
         RefEndpoint d = ref_endpoint(e.dst);
-        if (!d.ok || !names.count(d.node)) continue;
+        if (!d.ok || !rk.names.count(d.node)) continue;
         const std::string key = d.node + "." + d.endpoint + "#" + std::to_string(d.index);
         if (!buckets.count(key)) bucket_order.push_back(key);
         buckets[key].push_back({&e, d});
@@ -3181,7 +3207,7 @@ void check_reference_rules(const GraphDesc& g)
         const std::vector<Edge>& b = buckets[key];
         if (b.size() < 2) continue;
         const RefEndpoint& d = b[0].dst;
-        const RK dk = lookup(d.node, d.endpoint);
+        const RK dk = rk.lookup(d.node, d.endpoint);
         if (dk == RK::Value || dk == RK::Event) continue; // per-edge path: last write wins / event queues
         struct Src {
             ExprP x;
@@ -3202,11 +3228,11 @@ void check_reference_rules(const GraphDesc& g)
             std::vector<const Expr*> refs;
             collect_refs(s.x, refs);
             for (const Expr* r : refs)
-                if (names.count(r->node)) {
+                if (rk.names.count(r->node)) {
                     s.primary = r->node;
                     break;
                 }
-            if (kind_of(s.x) == RK::Event) any_event = true;
+            if (rk.kind_of(s.x) == RK::Event) any_event = true;
             srcs.push_back(s);
         }
         if (!parsed || any_event) continue;
@@ -3214,10 +3240,10 @@ void check_reference_rules(const GraphDesc& g)
         for (size_t k = 0; k < b.size(); ++k) {
             const Src& s = srcs[k];
             const char* what = nullptr;
-            const Named* sn = s.primary.empty() ? nullptr : &names[s.primary];
-            const Named& dn = names[d.node];
+            const RefKinds::Named* sn = s.primary.empty() ? nullptr : &rk.names[s.primary];
+            const RefKinds::Named& dn = rk.names[d.node];
             if (sn && sn->rate != dn.rate) what = "a cross-rate edge";
-            else if (!(s.ep.ok && names.count(s.ep.node)) || !sn) what = "a compound (non-endpoint) source";
+            else if (!(s.ep.ok && rk.names.count(s.ep.node)) || !sn) what = "a compound (non-endpoint) source";
             else if (sn->array_len && dn.array_len) what = "an array (parallel) source";
             else if (!sn->array_len && dn.array_len) what = "a broadcast source";
             else if (sn->array_len && !dn.array_len) what = "an array fan-in source";
@@ -3279,25 +3305,54 @@ int count_node_refs(const std::string& text, const std::string& name)
     }
     return n;
 }
-} // namespace
 
-std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::set<int>* zero_nodes, std::string* zero_body);
+// What the phases of lower() share besides Codegen: who reads whom, the ends of the post-mix stage, the emission order and
+// what the body writer takes over from the graph output.  Every phase is a member that lower() calls once, in the order
+// in which they are declared here (the list at lower() says what each reads and produces).
+struct Lowering {
+    Codegen& cg;
+    const GraphDesc& g;
+    CompiledGraph& out;
+    struct OutEdge {
+        ExprP src;
+        std::string policy;
+    };
+    std::map<int, std::vector<OutEdge>> out_edges; // graph output index -> sources
+    std::vector<std::set<int>> deps;               // node -> nodes it reads
+    std::vector<std::set<int>> out_deps;
+    std::vector<std::set<int>> out_reads;                    // output -> outputs its sources read (`out_a + out_b -> out`)
+    std::map<int, std::pair<int, std::string>> ev_out_edges; // graph EVENT output -> (node, event-output port) feeding it
+    std::vector<std::set<int>> fb_deps;                      // feedback edges: liveness only, no ordering
+    bool any_feedback = false;
+    int bus_conv_width = 1; // Convolver::<Frame<N>>: the N written in the node's type
+    int bus_src_output = -1, bus_final_output = -1;
+    std::vector<int> order;        // the live nodes in emission order
+    std::string bus_expr = "0.0f"; // what a frame of the voice puts onto the mix bus
+    int unroll = 2;                // frames per straight-line region of the ordinary kernel's quiet-chunk loop
 
-std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in) { return compile_pass(g_in, nullptr, nullptr); }
+    explicit Lowering(Codegen& c)
+        : cg(c), g(c.g), out(c.out), deps(g.nodes.size()), out_deps(g.outputs.size()), out_reads(g.outputs.size()), fb_deps(g.nodes.size())
+    {
+    }
+    int bus_node_of(const std::string& endpoint) const;
+    void declare_inputs_outputs();
+    void declare_nodes();
+    std::set<size_t> infer_overwritten_edges() const;
+    void wire_edges(const std::set<size_t>& overwritten);
+    void prune_dead_nodes();
+    void kahn_order();
+    void schedule_order();
+    void assign_rate_domains();
+    void plan_pipeline_stages();
+    void find_inner_event_sources();
+    void emit_nodes();
+    void form_graph_output();
+    void choose_unroll();
+};
 
-// zero_nodes == null: the general kernel (and, where the graph has ZeroChains, the zero variant next to it).  Otherwise the
-// zero variant's pass: stops once the kernel body is formed and returns it in *zero_body.
-std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::set<int>* zero_nodes, std::string* zero_body)
+// ---- inputs / outputs ----------------------------------------------------
+void Lowering::declare_inputs_outputs()
 {
-    check_reference_rules(g_in);
-    const GraphDesc g = expand(g_in);
-    auto cgp = std::make_unique<CompiledGraph>();
-    CompiledGraph& out = *cgp;
-    out.name = g.name;
-    Codegen cg(g, out);
-    cg.zero_nodes = zero_nodes;
-
-    // ---- inputs / outputs ----------------------------------------------------
     for (size_t i = 0; i < g.inputs.size(); ++i) {
         const GInput& in = g.inputs[i];
         if (cg.input_by_name.count(in.name)) fail("duplicate input '" + in.name + "'");
@@ -3328,10 +3383,12 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     for (auto& info : out.inputs)
         if (info.stream_row <= -2) info.stream_row = out.n_ramps + (-2 - info.stream_row);
     for (size_t i = 0; i < g.outputs.size(); ++i) cg.output_by_name[g.outputs[i].name] = (int)i;
+}
 
-    // ---- nodes ------------------------------------------------------------------
+// ---- nodes ------------------------------------------------------------------
+void Lowering::declare_nodes()
+{
     cg.nodes.resize(g.nodes.size());
-    int bus_conv_width = 1; // Convolver::<Frame<N>>: the N written in the node's type
     for (size_t i = 0; i < g.nodes.size(); ++i) {
         const GNode& nd = g.nodes[i];
         if (cg.node_by_name.count(nd.name) || cg.input_by_name.count(nd.name))
@@ -3385,144 +3442,144 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             fail("node type '" + nd.type + "' can only be used as a post-mix (bus) node");
         }
     }
+}
 
-    // ---- edges ------------------------------------------------------------------
-    struct OutEdge {
-        ExprP src;
-        std::string policy;
-    };
-    std::map<int, std::vector<OutEdge>> out_edges; // graph output index -> sources
-    std::vector<std::set<int>> deps(g.nodes.size()); // node -> nodes it reads
-    std::vector<std::set<int>> out_deps(g.outputs.size());
-    std::vector<std::set<int>> out_reads(g.outputs.size()); // output -> outputs its sources read (`out_a + out_b -> out`)
-    std::map<int, std::pair<int, std::string>> ev_out_edges; // graph EVENT output -> (node, event-output port) feeding it
-    std::vector<std::set<int>> fb_deps(g.nodes.size()); // feedback edges: liveness only, no ordering
-    bool any_feedback = false;
-    cg.emitted.assign(g.nodes.size(), 0);
-    auto bus_node_of = [&](const std::string& endpoint) -> int {
-        std::string nm = endpoint.substr(0, endpoint.find('.'));
-        while (!nm.empty() && isspace((unsigned char)nm.back())) nm.pop_back();
-        while (!nm.empty() && isspace((unsigned char)nm.front())) nm.erase(nm.begin());
-        auto it = cg.node_by_name.find(nm);
-        return (it != cg.node_by_name.end() && g.nodes[it->second].bus) ? it->second : -1;
-    };
-    int bus_src_output = -1, bus_final_output = -1;
-    // ---- endpoint kinds, as far as the reference's macro knows them (ir/lower.rs:233-338 infer_endpoint_types): typed
-    // graph inputs / outputs and stream-only policies seed kinds, connection statements propagate them both ways to a
-    // fixpoint; node-to-node endpoints nobody typed stay unknown.  Their one consequence (codegen/emit_node.rs:35-58
-    // classify_stream_fanin): SEVERAL edges into a destination known to be a VALUE are assigned one after the other --
-    // the last one wins -- while a stream or unknown destination gets their sum.
+// the post-mix (bus) node an edge endpoint names, or -1
+int Lowering::bus_node_of(const std::string& endpoint) const
+{
+    std::string nm = endpoint.substr(0, endpoint.find('.'));
+    while (!nm.empty() && isspace((unsigned char)nm.back())) nm.pop_back();
+    while (!nm.empty() && isspace((unsigned char)nm.front())) nm.erase(nm.begin());
+    auto it = cg.node_by_name.find(nm);
+    return (it != cg.node_by_name.end() && g.nodes[it->second].bus) ? it->second : -1;
+}
+
+// ---- endpoint kinds, as far as the reference's macro knows them (ir/lower.rs:233-338 infer_endpoint_types): typed
+// graph inputs / outputs and stream-only policies seed kinds, connection statements propagate them both ways to a
+// fixpoint; node-to-node endpoints nobody typed stay unknown.  Their one consequence (codegen/emit_node.rs:35-58
+// classify_stream_fanin): SEVERAL edges into a destination known to be a VALUE are assigned one after the other --
+// the last one wins -- while a stream or unknown destination gets their sum.
+// (check_reference_rules has an inference of its own -- reference_endpoint_kinds, before expansion, nothing inferred through a
+//  negation; this one runs after expansion, canonicalises array elements and lets a negation pass its operand's kind
+//  through.  They look alike and are deliberately not the same: not to be merged.)
+std::set<size_t> Lowering::infer_overwritten_edges() const
+{
     std::set<size_t> overwritten; // indices of g.edges a later edge into the same value destination replaces
-    {
-        enum K { Unknown = 0, Stream, Value, Event };
-        auto strip = [](std::string t) {
-            t.erase(std::remove_if(t.begin(), t.end(), [](char ch) { return isspace((unsigned char)ch); }), t.end());
-            return t;
-        };
-        // "node.port", keyed by the ROOT node of an expanded array element (`voices__3.cutoff` -> `voices.cutoff`): the
-        // reference infers one kind per (root node, field) and every element shares it (infer_endpoint_types runs before
-        // the array is unrolled, ir/lower.rs:233-338) -- ADVICE r3
-        auto canon = [](const std::string& key) {
-            const size_t dot = key.find('.');
-            std::string node = dot == std::string::npos ? key : key.substr(0, dot);
-            const size_t us = node.rfind("__");
-            if (us != std::string::npos && us + 2 < node.size() &&
-                std::all_of(node.begin() + (long)us + 2, node.end(), [](char ch) { return isdigit((unsigned char)ch); }))
-                node.erase(us);
-            return dot == std::string::npos ? node : node + key.substr(dot);
-        };
-        std::map<std::string, K> known;
-        auto decl_kind = [](Kind k) { return k == Kind::Stream ? Stream : (k == Kind::Value ? Value : Event); };
-        std::function<K(const ExprP&)> kind_of = [&](const ExprP& e) -> K {
-            if (!e) return Unknown;
-            switch (e->t) {
-            case Expr::Num: return Value;
-            case Expr::Ref: {
-                if (e->port.empty()) {
-                    auto ii = cg.input_by_name.find(e->node);
-                    if (ii != cg.input_by_name.end()) return decl_kind(g.inputs[ii->second].kind);
-                    auto oi = cg.output_by_name.find(e->node);
-                    return oi != cg.output_by_name.end() ? decl_kind(g.outputs[oi->second].kind) : Unknown;
-                }
-                auto it = known.find(canon(e->node + "." + e->port));
-                return it == known.end() ? Unknown : it->second;
+    enum K { Unknown = 0, Stream, Value, Event };
+    auto strip = [](std::string t) {
+        t.erase(std::remove_if(t.begin(), t.end(), [](char ch) { return isspace((unsigned char)ch); }), t.end());
+        return t;
+    };
+    // "node.port", keyed by the ROOT node of an expanded array element (`voices__3.cutoff` -> `voices.cutoff`): the
+    // reference infers one kind per (root node, field) and every element shares it (infer_endpoint_types runs before
+    // the array is unrolled, ir/lower.rs:233-338) -- ADVICE r3
+    auto canon = [](const std::string& key) {
+        const size_t dot = key.find('.');
+        std::string node = dot == std::string::npos ? key : key.substr(0, dot);
+        const size_t us = node.rfind("__");
+        if (us != std::string::npos && us + 2 < node.size() &&
+            std::all_of(node.begin() + (long)us + 2, node.end(), [](char ch) { return isdigit((unsigned char)ch); }))
+            node.erase(us);
+        return dot == std::string::npos ? node : node + key.substr(dot);
+    };
+    std::map<std::string, K> known;
+    auto decl_kind = [](Kind k) { return k == Kind::Stream ? Stream : (k == Kind::Value ? Value : Event); };
+    std::function<K(const ExprP&)> kind_of = [&](const ExprP& e) -> K {
+        if (!e) return Unknown;
+        switch (e->t) {
+        case Expr::Num: return Value;
+        case Expr::Ref: {
+            if (e->port.empty()) {
+                auto ii = cg.input_by_name.find(e->node);
+                if (ii != cg.input_by_name.end()) return decl_kind(g.inputs[ii->second].kind);
+                auto oi = cg.output_by_name.find(e->node);
+                return oi != cg.output_by_name.end() ? decl_kind(g.outputs[oi->second].kind) : Unknown;
             }
-            case Expr::Chan:
-            case Expr::Neg: return kind_of(e->a);
-            case Expr::Bin: {
-                const K l = kind_of(e->a), r = kind_of(e->b);
-                if (l == Unknown || r == Unknown || l == Event || r == Event) return Unknown;
-                return (l == Stream || r == Stream) ? Stream : Value;
-            }
-            default: return Unknown; // calls and methods: no type inference for arbitrary functions
-            }
-        };
-        struct Stmt {
-            size_t idx;
-            ExprP src;
-            std::string dst, src_endpoint; // dst: "node.port" or an output name; src_endpoint: set when the source is a plain node endpoint
-            bool dst_is_node;
-        };
-        std::vector<Stmt> stmts;
-        for (size_t idx = 0; idx < g.edges.size(); ++idx) {
-            const GEdge& e = g.edges[idx];
-            if (bus_node_of(e.dst) >= 0 || bus_node_of(e.src) >= 0) continue;
-            Stmt st;
-            st.idx = idx;
-            try {
-                st.src = Parser(e.src).parse();
-            } catch (const std::exception&) {
-                continue; // (reported by the pass below)
-            }
-            st.dst = strip(e.dst);
-            st.dst_is_node = st.dst.find('.') != std::string::npos;
-            if (st.src->t == Expr::Ref && !st.src->port.empty()) st.src_endpoint = st.src->node + "." + st.src->port;
-            if (e.policy == "linear" || e.policy == "sinc" || e.policy == "sinc_iir") { // stream-only kernels: both ends are streams
-                if (st.dst_is_node) known.emplace(canon(st.dst), Stream);
-                if (!st.src_endpoint.empty()) known.emplace(canon(st.src_endpoint), Stream);
-            }
-            stmts.push_back(st);
+            auto it = known.find(canon(e->node + "." + e->port));
+            return it == known.end() ? Unknown : it->second;
         }
-        for (size_t round = 0; round <= stmts.size(); ++round) {
-            bool changed = false;
-            for (const Stmt& st : stmts) {
-                const K sk = kind_of(st.src);
-                if (sk != Unknown && st.dst_is_node && !known.count(canon(st.dst))) {
-                    known[canon(st.dst)] = sk;
-                    changed = true;
-                }
-                K dk = Unknown;
-                if (st.dst_is_node) {
-                    auto it = known.find(canon(st.dst));
-                    dk = it == known.end() ? Unknown : it->second;
-                } else {
-                    auto oi = cg.output_by_name.find(st.dst);
-                    if (oi != cg.output_by_name.end()) dk = decl_kind(g.outputs[oi->second].kind);
-                }
-                if (dk != Unknown && !st.src_endpoint.empty() && !known.count(canon(st.src_endpoint))) {
-                    known[canon(st.src_endpoint)] = dk;
-                    changed = true;
-                }
-            }
-            if (!changed) break;
+        case Expr::Chan:
+        case Expr::Neg: return kind_of(e->a);
+        case Expr::Bin: {
+            const K l = kind_of(e->a), r = kind_of(e->b);
+            if (l == Unknown || r == Unknown || l == Event || r == Event) return Unknown;
+            return (l == Stream || r == Stream) ? Stream : Value;
         }
-        std::map<std::string, std::vector<size_t>> by_dst;
-        for (const Stmt& st : stmts)
-            if (!g.edges[st.idx].feedback) by_dst[st.dst].push_back(st.idx);
-        for (const auto& kv : by_dst) {
-            if (kv.second.size() < 2) continue;
+        default: return Unknown; // calls and methods: no type inference for arbitrary functions
+        }
+    };
+    struct Stmt {
+        size_t idx;
+        ExprP src;
+        std::string dst, src_endpoint; // dst: "node.port" or an output name; src_endpoint: set when the source is a plain node endpoint
+        bool dst_is_node;
+    };
+    std::vector<Stmt> stmts;
+    for (size_t idx = 0; idx < g.edges.size(); ++idx) {
+        const GEdge& e = g.edges[idx];
+        if (bus_node_of(e.dst) >= 0 || bus_node_of(e.src) >= 0) continue;
+        Stmt st;
+        st.idx = idx;
+        try {
+            st.src = Parser(e.src).parse();
+        } catch (const std::exception&) {
+            continue; // (reported by the pass below)
+        }
+        st.dst = strip(e.dst);
+        st.dst_is_node = st.dst.find('.') != std::string::npos;
+        if (st.src->t == Expr::Ref && !st.src->port.empty()) st.src_endpoint = st.src->node + "." + st.src->port;
+        if (e.policy == "linear" || e.policy == "sinc" || e.policy == "sinc_iir") { // stream-only kernels: both ends are streams
+            if (st.dst_is_node) known.emplace(canon(st.dst), Stream);
+            if (!st.src_endpoint.empty()) known.emplace(canon(st.src_endpoint), Stream);
+        }
+        stmts.push_back(st);
+    }
+    for (size_t round = 0; round <= stmts.size(); ++round) {
+        bool changed = false;
+        for (const Stmt& st : stmts) {
+            const K sk = kind_of(st.src);
+            if (sk != Unknown && st.dst_is_node && !known.count(canon(st.dst))) {
+                known[canon(st.dst)] = sk;
+                changed = true;
+            }
             K dk = Unknown;
-            if (kv.first.find('.') != std::string::npos) {
-                auto it = known.find(canon(kv.first));
+            if (st.dst_is_node) {
+                auto it = known.find(canon(st.dst));
                 dk = it == known.end() ? Unknown : it->second;
             } else {
-                auto oi = cg.output_by_name.find(kv.first);
+                auto oi = cg.output_by_name.find(st.dst);
                 if (oi != cg.output_by_name.end()) dk = decl_kind(g.outputs[oi->second].kind);
             }
-            if (dk == Value)
-                for (size_t k = 0; k + 1 < kv.second.size(); ++k) overwritten.insert(kv.second[k]);
+            if (dk != Unknown && !st.src_endpoint.empty() && !known.count(canon(st.src_endpoint))) {
+                known[canon(st.src_endpoint)] = dk;
+                changed = true;
+            }
         }
+        if (!changed) break;
     }
+    std::map<std::string, std::vector<size_t>> by_dst;
+    for (const Stmt& st : stmts)
+        if (!g.edges[st.idx].feedback) by_dst[st.dst].push_back(st.idx);
+    for (const auto& kv : by_dst) {
+        if (kv.second.size() < 2) continue;
+        K dk = Unknown;
+        if (kv.first.find('.') != std::string::npos) {
+            auto it = known.find(canon(kv.first));
+            dk = it == known.end() ? Unknown : it->second;
+        } else {
+            auto oi = cg.output_by_name.find(kv.first);
+            if (oi != cg.output_by_name.end()) dk = decl_kind(g.outputs[oi->second].kind);
+        }
+        if (dk == Value)
+            for (size_t k = 0; k + 1 < kv.second.size(); ++k) overwritten.insert(kv.second[k]);
+    }
+    return overwritten;
+}
+
+// ---- edges ------------------------------------------------------------------
+void Lowering::wire_edges(const std::set<size_t>& overwritten)
+{
+    cg.emitted.assign(g.nodes.size(), 0);
     for (size_t edge_index = 0; edge_index < g.edges.size(); ++edge_index) {
         const GEdge& e = g.edges[edge_index];
         if (overwritten.count(edge_index)) continue; // (a later edge into this value destination replaces it)
@@ -3661,8 +3718,11 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     // a node that receives another node's events runs after it (and keeps it alive)
     for (size_t i = 0; i < g.nodes.size(); ++i)
         for (const auto& kv : cg.nodes[i].ev_node_edges) deps[i].insert(kv.second.first);
+}
 
-    // ---- dead-node removal (ir/passes/dead_nodes.rs:11-62) ------------------------
+// ---- dead-node removal (ir/passes/dead_nodes.rs:11-62) ------------------------
+void Lowering::prune_dead_nodes()
+{
     if (!g.outputs.empty()) {
         std::vector<char> live(g.nodes.size(), 0);
         std::deque<int> q;
@@ -3703,100 +3763,104 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     // (array-valued graphs -- several lanes per voice: the per-voice scalars, event queues included, are replicated on the
     //  voice's lanes, every lane runs the handlers, and only the voice's lead lane logs a graph event output or counts a
     //  dropped push: og_kernel_rt.hip.h, VoiceCtx::lead)
+}
 
-    // ---- Kahn topological sort (ir/lower.rs:1015-1085), ready set in declaration order
-    std::vector<int> order;
-    {
-        std::vector<int> indeg(g.nodes.size(), 0);
-        std::vector<std::vector<int>> users(g.nodes.size());
-        for (size_t i = 0; i < g.nodes.size(); ++i) {
-            if (!cg.nodes[i].live) continue;
-            for (int d : deps[i]) {
-                if (d == (int)i) fail("node '" + g.nodes[i].name + "' feeds itself without a delay");
-                indeg[i]++;
-                users[d].push_back((int)i);
-            }
-        }
-        std::deque<int> ready;
-        size_t n_live = 0;
-        for (size_t i = 0; i < g.nodes.size(); ++i)
-            if (cg.nodes[i].live) {
-                ++n_live;
-                if (indeg[i] == 0) ready.push_back((int)i);
-            }
-        while (!ready.empty()) {
-            int n = ready.front();
-            ready.pop_front();
-            order.push_back(n);
-            for (int u : users[n])
-                if (--indeg[u] == 0) ready.push_back(u);
-        }
-        if (order.size() != n_live)
-            fail("graph contains a non-feedback cycle (use `-> [N] ->` to insert a delay buffer, or `-> [delay_node] ->` to "
-                 "route through a declared Delay node)");
-    }
-
-    // ---- schedule order (round 4).  The Kahn order above is the reference's; it front-loads every source node
-    // (FMVoice: the four envelopes, then the operators), which is the worst order for a pipeline cut: values live long,
-    // and the heavy chain sits entirely behind the light sources.  When the graph is a pure per-frame dataflow -- no
-    // feedback edge or delay (those read "the value of the previous frame", which depends on who runs first), no
-    // node-to-node event edge (delivery order), one rate, one lane per voice -- ANY topological order computes the same
-    // values bit for bit, so the nodes are emitted depth first from the sinks instead: a node's producers come right
-    // before it, heaviest producer chain first, light leaves (envelopes) just ahead of their consumer:
-    // FMVoice: env3 op3 route env2 op2 | mixer env1 op1 env_filter gain cutoff_mod filter output_gain -- the contiguous
-    // two-wave cut now balances (56 | 54 estimated VALU per frame; the Kahn order could only offer 47 | 63), every
-    // hand-off value but two stays inside its wave, and the ordinary kernel holds fewer values across nodes.
-    // OGC_ALAP=0 keeps the Kahn order (A/B).
-    {
-        bool any_delay_node = false;
-        for (int ni : order) any_delay_node = any_delay_node || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
-        bool any_rate = false;
-        for (int ni : order) any_rate = any_rate || cg.nodes[ni].decl->rate_factor != 1;
-        const bool reorder = !(ogabi::experiment_knob("OGC_ALAP") && atoi(ogabi::experiment_knob("OGC_ALAP")) == 0) && !any_feedback && !cg.dynamic_events && !any_delay_node &&
-                             !any_rate && out.lpv == 1 && order.size() >= 3;
-        if (reorder) {
-            std::vector<int> pos(g.nodes.size(), -1);
-            for (size_t k = 0; k < order.size(); ++k) pos[order[k]] = (int)k;
-            // weight of the not-yet-emitted producer cone of a node (memoised per call: the graphs are small)
-            std::vector<char> done(g.nodes.size(), 0);
-            std::function<int(int, std::set<int>&)> cone = [&](int n, std::set<int>& seen) -> int {
-                if (done[n] || !seen.insert(n).second) return 0;
-                int wsum = node_weight(cg.nodes[n].decl->type);
-                for (int d : deps[n]) wsum += cone(d, seen);
-                return wsum;
-            };
-            std::vector<int> sched;
-            std::function<void(int)> visit = [&](int n) {
-                if (done[n]) return;
-                std::vector<std::pair<int, int>> ds; // (-cone weight, Kahn position): heaviest chain first, ties in Kahn order
-                for (int d : deps[n]) {
-                    if (done[d] || !cg.nodes[d].live) continue;
-                    std::set<int> seen;
-                    ds.push_back({-cone(d, seen), pos[d]});
-                }
-                std::sort(ds.begin(), ds.end());
-                for (auto& pr : ds) visit(order[pr.second]);
-                done[n] = 1;
-                sched.push_back(n);
-            };
-            // sinks (nodes nobody reads) in Kahn order; what feeds the graph outputs comes last among them
-            std::vector<int> n_users(g.nodes.size(), 0);
-            for (int ni : order)
-                for (int d : deps[ni]) n_users[d]++;
-            for (int ni : order)
-                if (n_users[ni] == 0) visit(ni);
-            if (sched.size() == order.size()) {
-                for (int ni : order) out.node_order.push_back(g.nodes[ni].name); // the reference's (Kahn) order, for the record
-                order = sched;
-            }
+// ---- Kahn topological sort (ir/lower.rs:1015-1085), ready set in declaration order
+void Lowering::kahn_order()
+{
+    std::vector<int> indeg(g.nodes.size(), 0);
+    std::vector<std::vector<int>> users(g.nodes.size());
+    for (size_t i = 0; i < g.nodes.size(); ++i) {
+        if (!cg.nodes[i].live) continue;
+        for (int d : deps[i]) {
+            if (d == (int)i) fail("node '" + g.nodes[i].name + "' feeds itself without a delay");
+            indeg[i]++;
+            users[d].push_back((int)i);
         }
     }
+    std::deque<int> ready;
+    size_t n_live = 0;
+    for (size_t i = 0; i < g.nodes.size(); ++i)
+        if (cg.nodes[i].live) {
+            ++n_live;
+            if (indeg[i] == 0) ready.push_back((int)i);
+        }
+    while (!ready.empty()) {
+        int n = ready.front();
+        ready.pop_front();
+        order.push_back(n);
+        for (int u : users[n])
+            if (--indeg[u] == 0) ready.push_back(u);
+    }
+    if (order.size() != n_live)
+        fail("graph contains a non-feedback cycle (use `-> [N] ->` to insert a delay buffer, or `-> [delay_node] ->` to "
+             "route through a declared Delay node)");
+}
 
-    // (feedback edges in graphs with oversampled nodes: allowed when both ends tick at the same rate -- checked where
-    //  the consumer reads the previous tick's value, Codegen::eval)
+// ---- schedule order (round 4).  The Kahn order above is the reference's; it front-loads every source node
+// (FMVoice: the four envelopes, then the operators), which is the worst order for a pipeline cut: values live long,
+// and the heavy chain sits entirely behind the light sources.  When the graph is a pure per-frame dataflow -- no
+// feedback edge or delay (those read "the value of the previous frame", which depends on who runs first), no
+// node-to-node event edge (delivery order), one rate, one lane per voice -- ANY topological order computes the same
+// values bit for bit, so the nodes are emitted depth first from the sinks instead: a node's producers come right
+// before it, heaviest producer chain first, light leaves (envelopes) just ahead of their consumer:
+// FMVoice: env3 op3 route env2 op2 | mixer env1 op1 env_filter gain cutoff_mod filter output_gain -- the contiguous
+// two-wave cut now balances (56 | 54 estimated VALU per frame; the Kahn order could only offer 47 | 63), every
+// hand-off value but two stays inside its wave, and the ordinary kernel holds fewer values across nodes.
+// OGC_ALAP=0 keeps the Kahn order (A/B).
+void Lowering::schedule_order()
+{
+    bool any_delay_node = false;
+    for (int ni : order) any_delay_node = any_delay_node || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
+    bool any_rate = false;
+    for (int ni : order) any_rate = any_rate || cg.nodes[ni].decl->rate_factor != 1;
+    const bool reorder = !(ogabi::experiment_knob("OGC_ALAP") && atoi(ogabi::experiment_knob("OGC_ALAP")) == 0) && !any_feedback && !cg.dynamic_events && !any_delay_node &&
+                         !any_rate && out.lpv == 1 && order.size() >= 3;
+    if (reorder) {
+        std::vector<int> pos(g.nodes.size(), -1);
+        for (size_t k = 0; k < order.size(); ++k) pos[order[k]] = (int)k;
+        // weight of the not-yet-emitted producer cone of a node (memoised per call: the graphs are small)
+        std::vector<char> done(g.nodes.size(), 0);
+        std::function<int(int, std::set<int>&)> cone = [&](int n, std::set<int>& seen) -> int {
+            if (done[n] || !seen.insert(n).second) return 0;
+            int wsum = node_weight(cg.nodes[n].decl->type);
+            for (int d : deps[n]) wsum += cone(d, seen);
+            return wsum;
+        };
+        std::vector<int> sched;
+        std::function<void(int)> visit = [&](int n) {
+            if (done[n]) return;
+            std::vector<std::pair<int, int>> ds; // (-cone weight, Kahn position): heaviest chain first, ties in Kahn order
+            for (int d : deps[n]) {
+                if (done[d] || !cg.nodes[d].live) continue;
+                std::set<int> seen;
+                ds.push_back({-cone(d, seen), pos[d]});
+            }
+            std::sort(ds.begin(), ds.end());
+            for (auto& pr : ds) visit(order[pr.second]);
+            done[n] = 1;
+            sched.push_back(n);
+        };
+        // sinks (nodes nobody reads) in Kahn order; what feeds the graph outputs comes last among them
+        std::vector<int> n_users(g.nodes.size(), 0);
+        for (int ni : order)
+            for (int d : deps[ni]) n_users[d]++;
+        for (int ni : order)
+            if (n_users[ni] == 0) visit(ni);
+        if (sched.size() == order.size()) {
+            for (int ni : order) out.node_order.push_back(g.nodes[ni].name); // the reference's (Kahn) order, for the record
+            order = sched;
+        }
+    }
+}
 
-    // ---- rate domains (emit_frame.rs:183-215; taint analysis emit_node.rs:516-584) ------------
-    // 1 = oversampled inner loop; outer nodes downstream of an inner node run after the loop (2)
+// (feedback edges in graphs with oversampled nodes: allowed when both ends tick at the same rate -- checked where
+//  the consumer reads the previous tick's value, Codegen::eval)
+
+// ---- rate domains (emit_frame.rs:183-215; taint analysis emit_node.rs:516-584) ------------
+// 1 = oversampled inner loop; outer nodes downstream of an inner node run after the loop (2)
+void Lowering::assign_rate_domains()
+{
     for (int ni : order) {
         NodeInst& n = cg.nodes[ni];
         if (n.decl->rate_factor > 1) {
@@ -3811,251 +3875,254 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                 if (cg.nodes[d].domain >= 1) n.domain = 2;
         }
     }
+}
 
-    // ---- pipeline stages ------------------------------------------------------------------------
-    // With one wave per SIMD (65 536 voices on 1024 SIMDs) a lone wave retires an instruction only
-    // every ~6 cycles (dependent-instruction latency); more co-resident waves approach the ~3-cycle
-    // measured issue ceiling.
-    // The frame's node sequence is therefore also emitted as pipelines of two and of four waves over
-    // the same 64 voices: every node (or run of envelopes) is a stage; a wave takes a contiguous group
-    // of stages of balanced estimated VALU cost, works one hand-off chunk behind the previous wave,
-    // and the values that cross between waves travel through LDS.  The ordinary kernel is the single
-    // group of all stages.
+// ---- pipeline stages ------------------------------------------------------------------------
+// With one wave per SIMD (65 536 voices on 1024 SIMDs) a lone wave retires an instruction only
+// every ~6 cycles (dependent-instruction latency); more co-resident waves approach the ~3-cycle
+// measured issue ceiling.
+// The frame's node sequence is therefore also emitted as pipelines of two and of four waves over
+// the same 64 voices: every node (or run of envelopes) is a stage; a wave takes a contiguous group
+// of stages of balanced estimated VALU cost, works one hand-off chunk behind the previous wave,
+// and the values that cross between waves travel through LDS.  The ordinary kernel is the single
+// group of all stages.
+void Lowering::plan_pipeline_stages()
+{
     cg.stage_of.assign(g.nodes.size(), 0);
     cg.n_stages = 1;
     bool stereo_out = false;
+    const char* env_split = ogabi::experiment_knob("OGC_SPLIT");
+    bool any_delay = false; // delay lines are staged per chunk by the ordinary kernel only
+    for (int ni : order) any_delay = any_delay || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
+    for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
+    // a Frame<2> voice output (two bus tiles) is summed by the ordinary kernel only
+    std::function<int(const ExprP&)> width_of = [&](const ExprP& e) -> int {
+        if (!e) return 1;
+        if (e->t == Expr::Ref && !e->port.empty()) {
+            auto nit = cg.node_by_name.find(e->node);
+            if (nit == cg.node_by_name.end()) return 1;
+            const NodeTypeInfo* ti = cg.nodes[nit->second].type;
+            for (size_t o = 0; o < ti->outputs.size() && o < ti->out_channels.size(); ++o)
+                if (e->port == ti->outputs[o]) return ti->out_channels[o];
+            return 1;
+        }
+        if (e->t == Expr::Ref) { // a Frame<N> stream input of the graph
+            auto iit = cg.input_by_name.find(e->node);
+            return iit == cg.input_by_name.end() ? 1 : std::max(1, out.inputs[iit->second].decl.channels);
+        }
+        if (e->t == Expr::Chan || e->t == Expr::Method) return 1;
+        if (e->t == Expr::Call) {
+            if (e->port == "Frame") return (int)e->args.size();
+            const UserFunction* f = lookup_function(e->node, e->port);
+            return f ? f->result_channels : 1;
+        }
+        return std::max(width_of(e->a), width_of(e->b));
+    };
+    for (auto& kv : out_edges)
+        for (auto& src : kv.second) stereo_out = stereo_out || width_of(src.src) >= 2;
+    for (size_t oi = 0; oi < g.outputs.size(); ++oi) // (a declared `output out: stream: Frame<2>`)
+        stereo_out = stereo_out || (g.outputs[oi].kind == Kind::Stream && g.outputs[oi].channels >= 2);
+    // (several stream outputs = several bus channels: summed by the ordinary kernel only, like a Frame<2> output)
     {
-        const char* env_split = ogabi::experiment_knob("OGC_SPLIT");
-        bool any_delay = false; // delay lines are staged per chunk by the ordinary kernel only
-        for (int ni : order) any_delay = any_delay || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
-        for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
-        // a Frame<2> voice output (two bus tiles) is summed by the ordinary kernel only
-        std::function<int(const ExprP&)> width_of = [&](const ExprP& e) -> int {
-            if (!e) return 1;
-            if (e->t == Expr::Ref && !e->port.empty()) {
-                auto nit = cg.node_by_name.find(e->node);
-                if (nit == cg.node_by_name.end()) return 1;
-                const NodeTypeInfo* ti = cg.nodes[nit->second].type;
-                for (size_t o = 0; o < ti->outputs.size() && o < ti->out_channels.size(); ++o)
-                    if (e->port == ti->outputs[o]) return ti->out_channels[o];
-                return 1;
-            }
-            if (e->t == Expr::Ref) { // a Frame<N> stream input of the graph
-                auto iit = cg.input_by_name.find(e->node);
-                return iit == cg.input_by_name.end() ? 1 : std::max(1, out.inputs[iit->second].decl.channels);
-            }
-            if (e->t == Expr::Chan || e->t == Expr::Method) return 1;
-            if (e->t == Expr::Call) {
-                if (e->port == "Frame") return (int)e->args.size();
-                const UserFunction* f = lookup_function(e->node, e->port);
-                return f ? f->result_channels : 1;
-            }
-            return std::max(width_of(e->a), width_of(e->b));
-        };
-        for (auto& kv : out_edges)
-            for (auto& src : kv.second) stereo_out = stereo_out || width_of(src.src) >= 2;
-        for (size_t oi = 0; oi < g.outputs.size(); ++oi) // (a declared `output out: stream: Frame<2>`)
-            stereo_out = stereo_out || (g.outputs[oi].kind == Kind::Stream && g.outputs[oi].channels >= 2);
-        // (several stream outputs = several bus channels: summed by the ordinary kernel only, like a Frame<2> output)
-        {
-            int n_stream_outs = 0;
-            for (size_t oi = 0; oi < g.outputs.size(); ++oi)
-                if (g.outputs[oi].kind == Kind::Stream && out_edges.count((int)oi) && (int)oi != bus_src_output) ++n_stream_outs;
-            if (n_stream_outs > 1 && out.bus_stage != BusStage::Tremolo) stereo_out = true;
-        }
-        bool want = !(env_split && atoi(env_split) == 0) && cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
-                    !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
-        (void)stereo_out;
-        // estimated per-tick VALU cost of every node, in emission order
-        int total = 0;
-        std::vector<int> w;
-        for (int ni : order) {
-            const NodeInst& n = cg.nodes[ni];
-            int wt = node_weight(n.decl->type);
-            if (n.decl->type.rfind("TptFilter", 0) == 0) { // a cutoff fed by another node moves every sample: the
-                bool moving = false;                         // coefficient update (tan, reciprocal) runs on every tick
-                for (const char* port : {"cutoff", "q", "f_mod"}) {
-                    auto it = n.in_edges.find(port);
-                    if (it == n.in_edges.end()) continue;
-                    for (const auto& src : it->second) {
-                        std::vector<const Expr*> refs;
-                        collect_refs(src.e, refs);
-                        for (const Expr* r : refs) moving = moving || !r->port.empty();
-                    }
-                }
-                // (its true cost is ~45, but the grouping this weight gives for fm_voice -- op2 with the consumer wave --
-                //  measured equal on the default run and 12% faster at 98 304 voices than op2 with the producer)
-                wt = moving ? 12 : 9; // core 7 + the watched-input test + the coefficient update on the frames whose cutoff moved
-            }
-            w.push_back(wt);
-            total += wt;
-        }
-        // Stage = unit: a node, or a run of consecutive envelopes (their stage-end check is shared, see
-        // flush_post()).  At most 16 stages: the lightest adjacent pair is merged until they fit.
-        std::vector<int> unit_w, unit_end; // weight and one-past-last order index of every unit
-        for (size_t k = 0; k < order.size(); ++k) {
-            const bool env = cg.nodes[order[k]].decl->type.rfind("AdsrEnvelope::", 0) == 0;
-            const bool prev_env = k > 0 && cg.nodes[order[k - 1]].decl->type.rfind("AdsrEnvelope::", 0) == 0;
-            if (env && prev_env) {
-                unit_w.back() += w[k];
-                unit_end.back() = (int)k + 1;
-            } else {
-                unit_w.push_back(w[k]);
-                unit_end.push_back((int)k + 1);
-            }
-        }
-        while (unit_w.size() > 16) {
-            size_t best = 0;
-            for (size_t k = 0; k + 1 < unit_w.size(); ++k)
-                if (unit_w[k] + unit_w[k + 1] < unit_w[best] + unit_w[best + 1]) best = k;
-            unit_w[best] += unit_w[best + 1];
-            unit_end[best] = unit_end[best + 1];
-            unit_w.erase(unit_w.begin() + best + 1);
-            unit_end.erase(unit_end.begin() + best + 1);
-        }
-        // contiguous grouping of the stages into `parts` waves minimising the heaviest wave (the last wave
-        // also carries the mix-bus work); ties: smallest sum of squares
-        // (the wave that closes the chunk also transposes and reduces the bus tile and is the one everybody waits for:
-        //  interleaved A/B of the cuts, round 5 -- gain + add with the wave in front of the filter wave +1.5 .. +3.7 %)
-        const int BUS_W = 8;
-        // Values that cross a cut.  A value produced in one wave and read in another costs the producer an LDS store per
-        // frame, every reading wave an LDS load per frame AND eight registers (a chunk's hand-off values are fetched
-        // before its first tick): the cut {env2 op2 mixer env1}|{op1 env_filter gain add} balances the instruction counts
-        // better than {env2 op2 mixer}|{env1 op1 env_filter gain add} but reads one more value in its heaviest wave -- 92
-        // VGPRs instead of 80, five resident workgroups per CU instead of six, and measured 1.5 % slower
-        // (profiles/r05g_session6.log).  unit_of[node] = stage of every scheduled node; refs by (node, port).
-        std::map<std::string, int> unit_of_name;
-        {
-            int st = 0;
-            for (int k = 0; k < (int)order.size(); ++k) {
-                while (k >= unit_end[st]) ++st;
-                unit_of_name[cg.nodes[order[k]].decl->name] = st;
-            }
-        }
-        std::vector<std::set<std::pair<int, std::string>>> reads_of((size_t)unit_w.size()); // per stage: (producer stage, "node.port") it reads
-        for (int k = 0; k < (int)order.size(); ++k) {
-            const NodeInst& nd = cg.nodes[order[k]];
-            const int me = unit_of_name[nd.decl->name];
-            for (const auto& kv : nd.in_edges)
-                for (const auto& src : kv.second) {
+        int n_stream_outs = 0;
+        for (size_t oi = 0; oi < g.outputs.size(); ++oi)
+            if (g.outputs[oi].kind == Kind::Stream && out_edges.count((int)oi) && (int)oi != bus_src_output) ++n_stream_outs;
+        if (n_stream_outs > 1 && out.bus_stage != BusStage::Tremolo) stereo_out = true;
+    }
+    bool want = !(env_split && atoi(env_split) == 0) && cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
+                !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
+    (void)stereo_out;
+    // estimated per-tick VALU cost of every node, in emission order
+    int total = 0;
+    std::vector<int> w;
+    for (int ni : order) {
+        const NodeInst& n = cg.nodes[ni];
+        int wt = node_weight(n.decl->type);
+        if (n.decl->type.rfind("TptFilter", 0) == 0) { // a cutoff fed by another node moves every sample: the
+            bool moving = false;                         // coefficient update (tan, reciprocal) runs on every tick
+            for (const char* port : {"cutoff", "q", "f_mod"}) {
+                auto it = n.in_edges.find(port);
+                if (it == n.in_edges.end()) continue;
+                for (const auto& src : it->second) {
                     std::vector<const Expr*> refs;
                     collect_refs(src.e, refs);
-                    for (const Expr* r : refs) {
-                        auto it = unit_of_name.find(r->node);
-                        if (r->port.empty() || it == unit_of_name.end() || it->second == me) continue;
-                        reads_of[(size_t)me].insert({it->second, r->node + "." + r->port});
-                    }
+                    for (const Expr* r : refs) moving = moving || !r->port.empty();
                 }
+            }
+            // (its true cost is ~45, but the grouping this weight gives for fm_voice -- op2 with the consumer wave --
+            //  measured equal on the default run and 12% faster at 98 304 voices than op2 with the producer)
+            wt = moving ? 12 : 9; // core 7 + the watched-input test + the coefficient update on the frames whose cutoff moved
         }
-        std::set<std::pair<int, std::string>> bus_reads; // what the graph outputs read: consumed by the LAST wave
-        for (auto& kv : out_edges)
-            for (auto& src : kv.second) {
+        w.push_back(wt);
+        total += wt;
+    }
+    // Stage = unit: a node, or a run of consecutive envelopes (their stage-end check is shared, see
+    // flush_post()).  At most 16 stages: the lightest adjacent pair is merged until they fit.
+    std::vector<int> unit_w, unit_end; // weight and one-past-last order index of every unit
+    for (size_t k = 0; k < order.size(); ++k) {
+        const bool env = cg.nodes[order[k]].decl->type.rfind("AdsrEnvelope::", 0) == 0;
+        const bool prev_env = k > 0 && cg.nodes[order[k - 1]].decl->type.rfind("AdsrEnvelope::", 0) == 0;
+        if (env && prev_env) {
+            unit_w.back() += w[k];
+            unit_end.back() = (int)k + 1;
+        } else {
+            unit_w.push_back(w[k]);
+            unit_end.push_back((int)k + 1);
+        }
+    }
+    while (unit_w.size() > 16) {
+        size_t best = 0;
+        for (size_t k = 0; k + 1 < unit_w.size(); ++k)
+            if (unit_w[k] + unit_w[k + 1] < unit_w[best] + unit_w[best + 1]) best = k;
+        unit_w[best] += unit_w[best + 1];
+        unit_end[best] = unit_end[best + 1];
+        unit_w.erase(unit_w.begin() + best + 1);
+        unit_end.erase(unit_end.begin() + best + 1);
+    }
+    // contiguous grouping of the stages into `parts` waves minimising the heaviest wave (the last wave
+    // also carries the mix-bus work); ties: smallest sum of squares
+    // (the wave that closes the chunk also transposes and reduces the bus tile and is the one everybody waits for:
+    //  interleaved A/B of the cuts, round 5 -- gain + add with the wave in front of the filter wave +1.5 .. +3.7 %)
+    const int BUS_W = 8;
+    // Values that cross a cut.  A value produced in one wave and read in another costs the producer an LDS store per
+    // frame, every reading wave an LDS load per frame AND eight registers (a chunk's hand-off values are fetched
+    // before its first tick): the cut {env2 op2 mixer env1}|{op1 env_filter gain add} balances the instruction counts
+    // better than {env2 op2 mixer}|{env1 op1 env_filter gain add} but reads one more value in its heaviest wave -- 92
+    // VGPRs instead of 80, five resident workgroups per CU instead of six, and measured 1.5 % slower
+    // (profiles/r05g_session6.log).  unit_of[node] = stage of every scheduled node; refs by (node, port).
+    std::map<std::string, int> unit_of_name;
+    {
+        int st = 0;
+        for (int k = 0; k < (int)order.size(); ++k) {
+            while (k >= unit_end[st]) ++st;
+            unit_of_name[cg.nodes[order[k]].decl->name] = st;
+        }
+    }
+    std::vector<std::set<std::pair<int, std::string>>> reads_of((size_t)unit_w.size()); // per stage: (producer stage, "node.port") it reads
+    for (int k = 0; k < (int)order.size(); ++k) {
+        const NodeInst& nd = cg.nodes[order[k]];
+        const int me = unit_of_name[nd.decl->name];
+        for (const auto& kv : nd.in_edges)
+            for (const auto& src : kv.second) {
                 std::vector<const Expr*> refs;
-                collect_refs(src.src, refs);
+                collect_refs(src.e, refs);
                 for (const Expr* r : refs) {
                     auto it = unit_of_name.find(r->node);
-                    if (!r->port.empty() && it != unit_of_name.end()) bus_reads.insert({it->second, r->node + "." + r->port});
+                    if (r->port.empty() || it == unit_of_name.end() || it->second == me) continue;
+                    reads_of[(size_t)me].insert({it->second, r->node + "." + r->port});
                 }
             }
-        auto crossing = [&](int b0, int e, bool is_last) { // extra weight of the wave holding stages [b0, e)
-            std::set<std::string> in, outv;
-            for (int u = b0; u < e; ++u)
-                for (const auto& rd : reads_of[(size_t)u])
-                    if (rd.first < b0 || rd.first >= e) in.insert(rd.second);
-            if (is_last)
-                for (const auto& rd : bus_reads)
-                    if (rd.first < b0 || rd.first >= e) in.insert(rd.second);
-            for (int u = 0; u < (int)unit_w.size(); ++u) {
-                if (u >= b0 && u < e) continue;
-                for (const auto& rd : reads_of[(size_t)u])
-                    if (rd.first >= b0 && rd.first < e) outv.insert(rd.second);
+    }
+    std::set<std::pair<int, std::string>> bus_reads; // what the graph outputs read: consumed by the LAST wave
+    for (auto& kv : out_edges)
+        for (auto& src : kv.second) {
+            std::vector<const Expr*> refs;
+            collect_refs(src.src, refs);
+            for (const Expr* r : refs) {
+                auto it = unit_of_name.find(r->node);
+                if (!r->port.empty() && it != unit_of_name.end()) bus_reads.insert({it->second, r->node + "." + r->port});
             }
-            if (!is_last)
-                for (const auto& rd : bus_reads)
-                    if (rd.first >= b0 && rd.first < e) outv.insert(rd.second);
-            // (3 per value read -- load, wait and eight registers --, 1 per value written: with these the DP picks the cut
-            //  that measured best of six, {env3 op3 xf}|{env2 op2 mix}|{env1 op1 env_f gain add}|{filter gain bus};
-            //  2 per read picked {env3 op3 xf env2}|{op2 mix env1}|..., which measured worst)
-            return 3 * (int)in.size() + (int)outv.size();
+        }
+    auto crossing = [&](int b0, int e, bool is_last) { // extra weight of the wave holding stages [b0, e)
+        std::set<std::string> in, outv;
+        for (int u = b0; u < e; ++u)
+            for (const auto& rd : reads_of[(size_t)u])
+                if (rd.first < b0 || rd.first >= e) in.insert(rd.second);
+        if (is_last)
+            for (const auto& rd : bus_reads)
+                if (rd.first < b0 || rd.first >= e) in.insert(rd.second);
+        for (int u = 0; u < (int)unit_w.size(); ++u) {
+            if (u >= b0 && u < e) continue;
+            for (const auto& rd : reads_of[(size_t)u])
+                if (rd.first >= b0 && rd.first < e) outv.insert(rd.second);
+        }
+        if (!is_last)
+            for (const auto& rd : bus_reads)
+                if (rd.first >= b0 && rd.first < e) outv.insert(rd.second);
+        // (3 per value read -- load, wait and eight registers --, 1 per value written: with these the DP picks the cut
+        //  that measured best of six, {env3 op3 xf}|{env2 op2 mix}|{env1 op1 env_f gain add}|{filter gain bus};
+        //  2 per read picked {env3 op3 xf env2}|{op2 mix env1}|..., which measured worst)
+        return 3 * (int)in.size() + (int)outv.size();
+    };
+    auto grouping = [&](int parts) {
+        const int n = (int)unit_w.size();
+        std::vector<int> pre(n + 1, 0);
+        for (int k = 0; k < n; ++k) pre[k + 1] = pre[k] + unit_w[k];
+        struct Best {
+            long mx = 1L << 40, sq = 1L << 40;
+            std::vector<int> ends; // one-past-last stage of every wave
         };
-        auto grouping = [&](int parts) {
-            const int n = (int)unit_w.size();
-            std::vector<int> pre(n + 1, 0);
-            for (int k = 0; k < n; ++k) pre[k + 1] = pre[k] + unit_w[k];
-            struct Best {
-                long mx = 1L << 40, sq = 1L << 40;
-                std::vector<int> ends; // one-past-last stage of every wave
-            };
-            std::vector<std::vector<Best>> dp(parts + 1, std::vector<Best>(n + 1));
-            dp[0][0].mx = 0;
-            dp[0][0].sq = 0;
-            for (int p2 = 1; p2 <= parts; ++p2)
-                for (int e = p2; e <= n; ++e)
-                    for (int b0 = p2 - 1; b0 < e; ++b0) {
-                        const Best& prev = dp[p2 - 1][b0];
-                        if (prev.mx >= (1L << 40)) continue;
-                        const bool is_last = p2 == parts && e == n;
-                        const long wgt = pre[e] - pre[b0] + (is_last ? BUS_W : 0) + crossing(b0, e, is_last);
-                        const long mx = std::max(prev.mx, wgt), sq = prev.sq + wgt * wgt;
-                        Best& cur = dp[p2][e];
-                        if (mx < cur.mx || (mx == cur.mx && sq < cur.sq)) {
-                            cur.mx = mx;
-                            cur.sq = sq;
-                            cur.ends = prev.ends;
-                            cur.ends.push_back(e);
-                        }
+        std::vector<std::vector<Best>> dp(parts + 1, std::vector<Best>(n + 1));
+        dp[0][0].mx = 0;
+        dp[0][0].sq = 0;
+        for (int p2 = 1; p2 <= parts; ++p2)
+            for (int e = p2; e <= n; ++e)
+                for (int b0 = p2 - 1; b0 < e; ++b0) {
+                    const Best& prev = dp[p2 - 1][b0];
+                    if (prev.mx >= (1L << 40)) continue;
+                    const bool is_last = p2 == parts && e == n;
+                    const long wgt = pre[e] - pre[b0] + (is_last ? BUS_W : 0) + crossing(b0, e, is_last);
+                    const long mx = std::max(prev.mx, wgt), sq = prev.sq + wgt * wgt;
+                    Best& cur = dp[p2][e];
+                    if (mx < cur.mx || (mx == cur.mx && sq < cur.sq)) {
+                        cur.mx = mx;
+                        cur.sq = sq;
+                        cur.ends = prev.ends;
+                        cur.ends.push_back(e);
                     }
-            std::vector<std::vector<int>> groups;
+                }
+        std::vector<std::vector<int>> groups;
+        int lo = 0;
+        for (int e : dp[parts][n].ends) {
+            groups.emplace_back();
+            for (int k = lo; k < e; ++k) groups.back().push_back(k);
+            lo = e;
+        }
+        return groups;
+    };
+    if (want && total >= 34 && unit_w.size() >= 2) { // (thresholds in units of the round-5 node weights)
+        cg.n_stages = (int)unit_w.size();
+        int st = 0;
+        for (int k = 0; k < (int)order.size(); ++k) {
+            while (k >= unit_end[st]) ++st;
+            cg.stage_of[order[k]] = st;
+        }
+        cg.groups2 = grouping(2);
+        if (const char* ec = ogabi::experiment_knob("OGC_CUT2")) { // experiment knob: first wave = the first k stages
+            const int ku = std::max(1, std::min(cg.n_stages - 1, atoi(ec)));
+            cg.groups2 = {{}, {}};
+            for (int k = 0; k < cg.n_stages; ++k) cg.groups2[k < ku ? 0 : 1].push_back(k);
+        }
+        const char* ep = ogabi::experiment_knob("OGC_PARTS");
+        if (total >= 48 && unit_w.size() >= 4 && !(ep && atoi(ep) < 4)) cg.groups4 = grouping(ogabi::experiment_knob("OGC_K3") ? 3 : 4);
+        if (const char* ec = ogabi::experiment_knob("OGC_CUTS")) { // experiment knob: "a,b[,c]" = one-past-last stage of every wave but the last (3 or 4 waves)
+            std::vector<int> ends;
+            for (const char* q = ec; *q;) {
+                ends.push_back(atoi(q));
+                while (*q && *q != ',') ++q;
+                if (*q == ',') ++q;
+            }
+            ends.push_back(cg.n_stages);
+            std::vector<std::vector<int>> gr;
             int lo = 0;
-            for (int e : dp[parts][n].ends) {
-                groups.emplace_back();
-                for (int k = lo; k < e; ++k) groups.back().push_back(k);
+            bool ok = ends.size() >= 3 && ends.size() <= 6;
+            for (int e : ends) {
+                ok = ok && e > lo && e <= cg.n_stages;
+                gr.emplace_back();
+                for (int k = lo; k < e && ok; ++k) gr.back().push_back(k);
                 lo = e;
             }
-            return groups;
-        };
-        if (want && total >= 34 && unit_w.size() >= 2) { // (thresholds in units of the round-5 node weights)
-            cg.n_stages = (int)unit_w.size();
-            int st = 0;
-            for (int k = 0; k < (int)order.size(); ++k) {
-                while (k >= unit_end[st]) ++st;
-                cg.stage_of[order[k]] = st;
-            }
-            cg.groups2 = grouping(2);
-            if (const char* ec = ogabi::experiment_knob("OGC_CUT2")) { // experiment knob: first wave = the first k stages
-                const int ku = std::max(1, std::min(cg.n_stages - 1, atoi(ec)));
-                cg.groups2 = {{}, {}};
-                for (int k = 0; k < cg.n_stages; ++k) cg.groups2[k < ku ? 0 : 1].push_back(k);
-            }
-            const char* ep = ogabi::experiment_knob("OGC_PARTS");
-            if (total >= 48 && unit_w.size() >= 4 && !(ep && atoi(ep) < 4)) cg.groups4 = grouping(ogabi::experiment_knob("OGC_K3") ? 3 : 4);
-            if (const char* ec = ogabi::experiment_knob("OGC_CUTS")) { // experiment knob: "a,b[,c]" = one-past-last stage of every wave but the last (3 or 4 waves)
-                std::vector<int> ends;
-                for (const char* q = ec; *q;) {
-                    ends.push_back(atoi(q));
-                    while (*q && *q != ',') ++q;
-                    if (*q == ',') ++q;
-                }
-                ends.push_back(cg.n_stages);
-                std::vector<std::vector<int>> gr;
-                int lo = 0;
-                bool ok = ends.size() >= 3 && ends.size() <= 6;
-                for (int e : ends) {
-                    ok = ok && e > lo && e <= cg.n_stages;
-                    gr.emplace_back();
-                    for (int k = lo; k < e && ok; ++k) gr.back().push_back(k);
-                    lo = e;
-                }
-                if (ok) cg.groups4 = gr;
-            }
+            if (ok) cg.groups4 = gr;
         }
     }
     cg.split = cg.n_stages > 1;
+}
 
-
-    // ---- event outputs read inside the oversampled region (step 6a, see Sect::s_ev6a): which they are, and the queue
-    // capacity of the graph BEFORE any node is emitted (such a queue collects the pushes of all N inner ticks of a frame
-    // and is a state plane per slot)
+// ---- event outputs read inside the oversampled region (step 6a, see Sect::s_ev6a): which they are, and the queue
+// capacity of the graph BEFORE any node is emitted (such a queue collects the pushes of all N inner ticks of a frame
+// and is a state plane per slot)
+void Lowering::find_inner_event_sources()
+{
     for (int ni : order) {
         const NodeInst& n = cg.nodes[ni];
         if (n.type->user && !n.type->user->ev_outputs.empty() && n.type->user->event_capacity > cg.ev_capacity)
@@ -4075,8 +4142,11 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                     fail_unsupported("event output '" + src.decl->name + "." + kv.second.second + "' feeds both an oversampled node and a graph event output");
         }
     }
+}
 
-    // ---- emit nodes: outer (pre), inner, outer (post), each in topological order -------------
+// ---- emit nodes: outer (pre), inner, outer (post), each in topological order -------------
+void Lowering::emit_nodes()
+{
     for (int dom = 0; dom < 3; ++dom) {
         cg.dom = dom;
         for (int ni : order) {
@@ -4094,139 +4164,139 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         }
         cg.flush_post();
     }
+}
 
-    // ---- graph output (outer rate, last stage) -------------------------------------------------
-    std::string bus_expr = "0.0f";
+// ---- graph output (outer rate, last stage) -------------------------------------------------
+void Lowering::form_graph_output()
+{
     cg.dom = 2;
     cg.cs = cg.n_stages - 1;
+    int n_stream = 0;
+    // outputs that other outputs read come first (`[sinc] a.output -> out_a; out_a + out_b -> out`); such an output
+    // is a named per-frame value of the voice, the output nobody reads is the one that goes onto the mix bus
+    std::vector<int> consumed(g.outputs.size(), 0);
+    for (const auto& rd : out_reads)
+        for (int so : rd) consumed[so] = 1;
+    std::vector<size_t> oorder;
     {
-        int n_stream = 0;
-        // outputs that other outputs read come first (`[sinc] a.output -> out_a; out_a + out_b -> out`); such an output
-        // is a named per-frame value of the voice, the output nobody reads is the one that goes onto the mix bus
-        std::vector<int> consumed(g.outputs.size(), 0);
-        for (const auto& rd : out_reads)
-            for (int so : rd) consumed[so] = 1;
-        std::vector<size_t> oorder;
-        {
-            std::vector<int> done(g.outputs.size(), 0);
-            for (size_t pass = 0; pass <= g.outputs.size() && oorder.size() < g.outputs.size(); ++pass)
-                for (size_t oi = 0; oi < g.outputs.size(); ++oi) {
-                    if (done[oi]) continue;
-                    bool ready = true;
-                    for (int so : out_reads[oi]) ready = ready && done[so];
-                    if (!ready) continue;
-                    done[oi] = 1;
-                    oorder.push_back(oi);
-                }
-            if (oorder.size() < g.outputs.size()) fail("graph outputs read each other in a cycle");
+        std::vector<int> done(g.outputs.size(), 0);
+        for (size_t pass = 0; pass <= g.outputs.size() && oorder.size() < g.outputs.size(); ++pass)
+            for (size_t oi = 0; oi < g.outputs.size(); ++oi) {
+                if (done[oi]) continue;
+                bool ready = true;
+                for (int so : out_reads[oi]) ready = ready && done[so];
+                if (!ready) continue;
+                done[oi] = 1;
+                oorder.push_back(oi);
+            }
+        if (oorder.size() < g.outputs.size()) fail("graph outputs read each other in a cycle");
+    }
+    for (size_t oi = 0; oi < g.outputs.size(); ++oi) { // event outputs: one log call per frame each, before the clears
+        if (g.outputs[oi].kind != Kind::Event) continue;
+        auto eo = ev_out_edges.find((int)oi);
+        if (eo == ev_out_edges.end()) continue; // declared, never fed: nothing ever arrives
+        const NodeInst& src = cg.nodes[eo->second.first];
+        const std::string q = "n" + std::to_string(src.id) + "_" + eo->second.second;
+        // an oversampled node's queue is cleared after every INNER tick: its events are logged there, all N ticks of
+        // outer frame f under frame f (the inner -> outer rescale of a cross-rate event edge, ir/lower.rs:846-852)
+        std::ostringstream& log = src.domain == 1 ? cg.sec[cg.stage_of.size() > (size_t)src.id ? cg.stage_of[src.id] : 0].s_log : cg.frame_log;
+        log << (src.domain == 1 ? "    " : "") << "        if (__any((int)(" << q << ".n != 0u))) og::ev_out_log(A, c, " << out.event_outputs.size() << "u, f, " << q << ");\n";
+        out.event_outputs.push_back(g.outputs[oi].name);
+    }
+    std::vector<int> formed(g.outputs.size(), 0); // channels of every stream output that has sources
+    for (size_t oi : oorder) {
+        if (g.outputs[oi].kind == Kind::Event) continue;
+        auto it = out_edges.find((int)oi);
+        if (it == out_edges.end()) {
+            if (consumed[oi]) fail("graph output '" + g.outputs[oi].name + "' is read but nothing feeds it");
+            continue;
         }
-        for (size_t oi = 0; oi < g.outputs.size(); ++oi) { // event outputs: one log call per frame each, before the clears
-            if (g.outputs[oi].kind != Kind::Event) continue;
-            auto eo = ev_out_edges.find((int)oi);
-            if (eo == ev_out_edges.end()) continue; // declared, never fed: nothing ever arrives
-            const NodeInst& src = cg.nodes[eo->second.first];
-            const std::string q = "n" + std::to_string(src.id) + "_" + eo->second.second;
-            // an oversampled node's queue is cleared after every INNER tick: its events are logged there, all N ticks of
-            // outer frame f under frame f (the inner -> outer rescale of a cross-rate event edge, ir/lower.rs:846-852)
-            std::ostringstream& log = src.domain == 1 ? cg.sec[cg.stage_of.size() > (size_t)src.id ? cg.stage_of[src.id] : 0].s_log : cg.frame_log;
-            log << (src.domain == 1 ? "    " : "") << "        if (__any((int)(" << q << ".n != 0u))) og::ev_out_log(A, c, " << out.event_outputs.size() << "u, f, " << q << ");\n";
-            out.event_outputs.push_back(g.outputs[oi].name);
-        }
-        std::vector<int> formed(g.outputs.size(), 0); // channels of every stream output that has sources
-        for (size_t oi : oorder) {
-            if (g.outputs[oi].kind == Kind::Event) continue;
-            auto it = out_edges.find((int)oi);
-            if (it == out_edges.end()) {
-                if (consumed[oi]) fail("graph output '" + g.outputs[oi].name + "' is read but nothing feeds it");
+        if ((int)oi == bus_final_output) fail("graph output fed by the post-mix node cannot have other sources");
+        ++n_stream;
+        // a Frame<N> voice (N = 2..4): every channel summed over the voices, bus interleaved (BlockRender<Frame<N>>)
+        std::vector<std::string> acc; // one accumulated expression per channel
+        int width = 0;                // 1 = f32, N = Frame<N>
+        for (size_t k = 0; k < it->second.size(); ++k) {
+            if (it->second.size() > 1 && !it->second[k].policy.empty())
+                fail("fan-in summing supports only same-rate sources (graph output)");
+            Val v = cg.cross(cg.eval(it->second[k].src), it->second[k].policy, false, false);
+            const int w = v.is_frame() ? (int)v.ch.size() : 1;
+            if (w > 4) fail("graph output '" + g.outputs[oi].name + "' is fed a Frame<" + std::to_string(w) + ">: the mix bus carries f32 or Frame<2..4> voices");
+            if (k > 0 && w != width)
+                fail("graph output '" + g.outputs[oi].name + "' mixes " + (width > 1 ? "Frame<" + std::to_string(width) + ">" : std::string("f32")) +
+                     " and " + (w > 1 ? "Frame<" + std::to_string(w) + ">" : std::string("f32")) + " sources");
+            width = w;
+            if (w > 1) {
+                if (out.bus_stage == BusStage::Tremolo) // (array-valued voices: the voice's lead lane puts every channel, og::bus_put)
+                    fail_unsupported("a Frame<N> graph output is not supported in post-mix graphs yet");
+                if (k == 0) acc.assign((size_t)w, std::string());
+                for (int c = 0; c < w; ++c) acc[(size_t)c] = (k == 0) ? v.ch[(size_t)c].e : "(" + acc[(size_t)c] + " + " + v.ch[(size_t)c].e + ")";
                 continue;
             }
-            if ((int)oi == bus_final_output) fail("graph output fed by the post-mix node cannot have other sources");
-            ++n_stream;
-            // a Frame<N> voice (N = 2..4): every channel summed over the voices, bus interleaved (BlockRender<Frame<N>>)
-            std::vector<std::string> acc; // one accumulated expression per channel
-            int width = 0;                // 1 = f32, N = Frame<N>
-            for (size_t k = 0; k < it->second.size(); ++k) {
-                if (it->second.size() > 1 && !it->second[k].policy.empty())
-                    fail("fan-in summing supports only same-rate sources (graph output)");
-                Val v = cg.cross(cg.eval(it->second[k].src), it->second[k].policy, false, false);
-                const int w = v.is_frame() ? (int)v.ch.size() : 1;
-                if (w > 4) fail("graph output '" + g.outputs[oi].name + "' is fed a Frame<" + std::to_string(w) + ">: the mix bus carries f32 or Frame<2..4> voices");
-                if (k > 0 && w != width)
-                    fail("graph output '" + g.outputs[oi].name + "' mixes " + (width > 1 ? "Frame<" + std::to_string(width) + ">" : std::string("f32")) +
-                         " and " + (w > 1 ? "Frame<" + std::to_string(w) + ">" : std::string("f32")) + " sources");
-                width = w;
-                if (w > 1) {
-                    if (out.bus_stage == BusStage::Tremolo) // (array-valued voices: the voice's lead lane puts every channel, og::bus_put)
-                        fail_unsupported("a Frame<N> graph output is not supported in post-mix graphs yet");
-                    if (k == 0) acc.assign((size_t)w, std::string());
-                    for (int c = 0; c < w; ++c) acc[(size_t)c] = (k == 0) ? v.ch[(size_t)c].e : "(" + acc[(size_t)c] + " + " + v.ch[(size_t)c].e + ")";
-                    continue;
-                }
-                if (it->second.size() > 1 && v.inner) fail("fan-in summing supports only same-rate sources (graph output)");
-                if (k == 0) acc.assign(1, std::string());
-                acc[0] = (k == 0) ? v.e : "(" + acc[0] + " + " + v.e + ")";
-            }
-            const int declared = g.outputs[oi].channels; // `output out: stream: Frame<2>;` (0: not declared)
-            if (declared > 4) fail("graph output '" + g.outputs[oi].name + "': the mix bus carries f32 or Frame<2..4> voices");
-            if (declared && declared != width)
-                fail("graph output '" + g.outputs[oi].name + "' is declared " + (declared > 1 ? "Frame<" + std::to_string(declared) + ">" : std::string("f32")) +
-                     " but fed " + (width > 1 ? "a Frame<" + std::to_string(width) + ">" : std::string("an f32 stream")));
-            // every stream output is a named value of this frame: other outputs may read it (`out_a + out_b -> out`),
-            // and ALL of them go onto the mix bus, one channel (Frame<N>: N) each, in declaration order
-            const std::string var = "go" + std::to_string(oi);
-            auto chan_name = [&](int c) { // (Frame<2> keeps its _l / _r names: the text of existing kernels does not move)
-                return width == 2 ? var + (c == 0 ? "_l" : "_r") : var + "_c" + std::to_string(c);
-            };
-            Val ov;
-            ov.rate = Rate::Vary;
-            if (width > 1) {
-                cg.os() << "        const float ";
-                for (int c = 0; c < width; ++c) {
-                    cg.os() << (c ? ", " : "") << chan_name(c) << " = " << acc[(size_t)c];
-                    Val cv;
-                    cv.rate = Rate::Vary;
-                    cv.e = chan_name(c);
-                    ov.ch.push_back(cv);
-                }
-                cg.os() << ";\n";
-            } else {
-                cg.os() << "        const float " << var << " = " << acc[0] << ";\n";
-                ov.e = var;
-            }
-            cg.output_vals[g.outputs[oi].name] = ov;
-            formed[oi] = width;
+            if (it->second.size() > 1 && v.inner) fail("fan-in summing supports only same-rate sources (graph output)");
+            if (k == 0) acc.assign(1, std::string());
+            acc[0] = (k == 0) ? v.e : "(" + acc[0] + " + " + v.e + ")";
         }
-        // the bus: the formed stream outputs in DECLARATION order
-        std::vector<std::string> chans;
-        for (size_t oi = 0; oi < g.outputs.size(); ++oi) {
-            if (!formed[oi]) continue;
-            const std::string var = "go" + std::to_string(oi);
-            out.output_channels.push_back({g.outputs[oi].name, (int)chans.size(), formed[oi]});
-            if (formed[oi] == 2) {
-                chans.push_back(var + "_l");
-                chans.push_back(var + "_r");
-            } else if (formed[oi] > 2) {
-                for (int c = 0; c < formed[oi]; ++c) chans.push_back(var + "_c" + std::to_string(c));
-            } else {
-                chans.push_back(var);
+        const int declared = g.outputs[oi].channels; // `output out: stream: Frame<2>;` (0: not declared)
+        if (declared > 4) fail("graph output '" + g.outputs[oi].name + "': the mix bus carries f32 or Frame<2..4> voices");
+        if (declared && declared != width)
+            fail("graph output '" + g.outputs[oi].name + "' is declared " + (declared > 1 ? "Frame<" + std::to_string(declared) + ">" : std::string("f32")) +
+                 " but fed " + (width > 1 ? "a Frame<" + std::to_string(width) + ">" : std::string("an f32 stream")));
+        // every stream output is a named value of this frame: other outputs may read it (`out_a + out_b -> out`),
+        // and ALL of them go onto the mix bus, one channel (Frame<N>: N) each, in declaration order
+        const std::string var = "go" + std::to_string(oi);
+        auto chan_name = [&](int c) { // (Frame<2> keeps its _l / _r names: the text of existing kernels does not move)
+            return width == 2 ? var + (c == 0 ? "_l" : "_r") : var + "_c" + std::to_string(c);
+        };
+        Val ov;
+        ov.rate = Rate::Vary;
+        if (width > 1) {
+            cg.os() << "        const float ";
+            for (int c = 0; c < width; ++c) {
+                cg.os() << (c ? ", " : "") << chan_name(c) << " = " << acc[(size_t)c];
+                Val cv;
+                cv.rate = Rate::Vary;
+                cv.e = chan_name(c);
+                ov.ch.push_back(cv);
             }
+            cg.os() << ";\n";
+        } else {
+            cg.os() << "        const float " << var << " = " << acc[0] << ";\n";
+            ov.e = var;
         }
-        if (chans.size() > 1 && out.bus_stage == BusStage::Tremolo)
-            fail_unsupported("several bus channels (stream outputs / Frame<2>) are not supported in post-mix graphs yet");
-        if (chans.size() > 4) fail("the mix bus carries at most 4 channels (stream outputs, a Frame<N> counting N)");
-        if (chans.size() == 1) {
-            cg.os() << "        const float g_out = " << chans[0] << ";\n";
-            bus_expr = "g_out";
-        } else if (chans.size() > 1) {
-            cg.os() << "        const og::OutN<" << chans.size() << "> g_out = {{";
-            for (size_t k = 0; k < chans.size(); ++k) cg.os() << (k ? ", " : "") << chans[k];
-            cg.os() << "}};\n";
-            out.voice_channels = (uint32_t)chans.size();
-            out.channels = (uint32_t)chans.size();
-            bus_expr = "g_out";
-        }
-        (void)n_stream;
+        cg.output_vals[g.outputs[oi].name] = ov;
+        formed[oi] = width;
     }
+    // the bus: the formed stream outputs in DECLARATION order
+    std::vector<std::string> chans;
+    for (size_t oi = 0; oi < g.outputs.size(); ++oi) {
+        if (!formed[oi]) continue;
+        const std::string var = "go" + std::to_string(oi);
+        out.output_channels.push_back({g.outputs[oi].name, (int)chans.size(), formed[oi]});
+        if (formed[oi] == 2) {
+            chans.push_back(var + "_l");
+            chans.push_back(var + "_r");
+        } else if (formed[oi] > 2) {
+            for (int c = 0; c < formed[oi]; ++c) chans.push_back(var + "_c" + std::to_string(c));
+        } else {
+            chans.push_back(var);
+        }
+    }
+    if (chans.size() > 1 && out.bus_stage == BusStage::Tremolo)
+        fail_unsupported("several bus channels (stream outputs / Frame<2>) are not supported in post-mix graphs yet");
+    if (chans.size() > 4) fail("the mix bus carries at most 4 channels (stream outputs, a Frame<N> counting N)");
+    if (chans.size() == 1) {
+        cg.os() << "        const float g_out = " << chans[0] << ";\n";
+        bus_expr = "g_out";
+    } else if (chans.size() > 1) {
+        cg.os() << "        const og::OutN<" << chans.size() << "> g_out = {{";
+        for (size_t k = 0; k < chans.size(); ++k) cg.os() << (k ? ", " : "") << chans[k];
+        cg.os() << "}};\n";
+        out.voice_channels = (uint32_t)chans.size();
+        out.channels = (uint32_t)chans.size();
+        bus_expr = "g_out";
+    }
+    (void)n_stream;
     if (out.bus_stage == BusStage::Convolver && bus_conv_width > 1 && (uint32_t)bus_conv_width != out.voice_channels)
         fail("the post-mix Convolver is a Convolver::<Frame<" + std::to_string(bus_conv_width) + ">> but the summed voices have " +
              std::to_string(out.voice_channels) + " channel(s)");
@@ -4234,9 +4304,77 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     out.max_pipeline = !cg.groups4.empty() ? 4 : (!cg.groups2.empty() ? 2 : 1);
 
     if (out.n_slots > 160) fail("graph needs more than 160 uniform slots");
+}
 
-    // per-stage pieces of the kernel body
-    auto tick_code = [&](int st) {
+// frames per straight-line scheduling region of the ordinary kernel's quiet-chunk loop.  A large graph with
+// envelopes has three copies of the chunk body (no stage-end checks / no release arithmetic) and sits at the
+// 128-VGPR cap: unrolling by two spills ~20 registers there (fm_voice: 2-4% slower at >= 131 072 voices, where
+// this kernel runs); small graphs gain from it (4x saturator +5%).
+void Lowering::choose_unroll()
+{
+    int graph_weight = 0;
+    bool has_env = false;
+    for (int ni : order) {
+        graph_weight += node_weight(cg.nodes[ni].decl->type);
+        has_env = has_env || cg.nodes[ni].decl->type.rfind("AdsrEnvelope::", 0) == 0;
+    }
+    out.valu_estimate = graph_weight + 8; // + the mix bus
+    unroll = (has_env && graph_weight >= 100) ? 1 : 2;
+    // Round 6: the whole 16-frame bus chunk as ONE straight-line region wherever registers allow.  A value that lives across
+    // frames -- the saturator's four half-band histories (62 live samples that shift every frame), phases, filter states --
+    // crosses the loop's back edge once per trip and has to sit where the loop head expects it: with two frames per trip the
+    // histories were copied on every trip (20 v_mov per frame of 162 VALU); with sixteen a sample is written straight into the
+    // register it will be read from a chunk later.  Interleaved A/B on one MI355X (profiles/r06_handoff_ab.md, r07f / r07g):
+    // SatGraph_4x 131 072 voices 3.33e11 -> 3.50 / 3.61 / 3.71e11 at 4 / 8 / 16; fm_voice 262 144 6.88e11 -> 6.97 / 6.92 /
+    // 7.02e11, 1 048 576 8.06e11 -> 8.17 / 8.06 / 8.17e11; osc+env+TPT 1.125e12 -> 1.157 / 1.161 / 1.153e12; the delay-line
+    // voice 5.21e11 -> 5.32 / 5.28 / 5.17e11 (its chunk is bracketed by the ring staging: four frames per trip); the
+    // electric piano does not move (its harmonics are not shifted) and keeps its two.  (The pipelined shapes always
+    // unrolled their chunks.)
+    if (unroll > 1) {
+        if (out.lpv > 1) unroll = 2;
+        else if (!out.rings.empty()) unroll = 4;
+        else if (!out.players.empty()) unroll = 16; // (a tick shifts the chunk's staged frames down: renames in a straight-line chunk)
+        else if (cg.N > 1) unroll = 16;
+        else unroll = (has_env && graph_weight >= 70) ? 4 : 8; // (fm_voice: sixteen is worth +0.7 % over four and brings spills into the tapped variants' chunk bodies)
+    }
+    if (const char* u = ogabi::experiment_knob("OGC_UNROLL")) unroll = std::max(1, std::min(16, atoi(u)));
+}
+
+// ---- the body writer: the kernel text of a lowered graph, assembled from the per-stage sections the nodes wrote --------
+struct BodyWriter {
+    Codegen& cg;
+    const GraphDesc& g;
+    CompiledGraph& out;
+    const std::vector<int>& order;
+    const std::string& bus_expr;
+    const int unroll;
+    std::vector<int> all_stages;
+    const bool chunk_chk; // the chunk variants without stage-end checks exist (OGC_CHUNK_CHK=0 / node-to-node events: off)
+    std::ostringstream body;
+
+    explicit BodyWriter(const Lowering& lw)
+        : cg(lw.cg), g(lw.g), out(lw.out), order(lw.order), bus_expr(lw.bus_expr), unroll(lw.unroll),
+          chunk_chk(!(ogabi::experiment_knob("OGC_CHUNK_CHK") && atoi(ogabi::experiment_knob("OGC_CHUNK_CHK")) == 0) && !cg.dynamic_events)
+    {
+        for (int k = 0; k < cg.n_stages; ++k) all_stages.push_back(k);
+    }
+    std::string tick_code(int st);
+    std::string events_code(const std::vector<int>& stages, bool prefetch = true);
+    std::string vin_store();
+    std::string cat(const std::vector<int>& st, std::ostringstream Codegen::Sect::*m);
+    static int group_of(const std::vector<std::vector<int>>& groups, int stage);
+    std::string group_tick(const std::vector<std::vector<int>>& groups, int gi);
+    std::string min_cnt(const std::vector<int>& st);
+    std::string rs_sum(const std::vector<int>& st);
+    std::string fc_sync(const std::vector<int>& st, const std::string& ind);
+    void write_ordinary_kernel();
+    void pipeline_lds(const std::vector<std::vector<int>>& groups);
+    void write_pipeline_kernel(const std::vector<std::vector<int>>& groups, int tag);
+};
+
+// per-stage pieces of the kernel body
+std::string BodyWriter::tick_code(int st)
+{
         Codegen::Sect& S = cg.sec[st];
         std::ostringstream t;
         t << S.s_pre.str() << S.s_up.str() << S.s_ev6a.str() << S.s_ev6a_clear.str();
@@ -4245,9 +4383,11 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
               << S.s_inner.str() << S.s_log.str() << S.s_cap.str() << "        }\n";
         t << S.s_down.str() << S.s_post.str();
         return t.str();
-    };
-    // per-voice events due on frame f (sub-block splitting of process_block, codegen/mod.rs:836-871)
-    auto events_code = [&](const std::vector<int>& stages, bool prefetch = true) {
+}
+
+// per-voice events due on frame f (sub-block splitting of process_block, codegen/mod.rs:836-871)
+std::string BodyWriter::events_code(const std::vector<int>& stages, bool prefetch)
+{
         const std::string PRE = prefetch ? "true" : "false"; // (the ordinary kernel reads the record when it fires: og::ev_arm)
         std::ostringstream t;
         t << "    auto events = [&](const uint32_t f) __attribute__((always_inline)) {\n"
@@ -4275,8 +4415,10 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
           << "            } while (c.next_ev <= f);\n"
           << "        }\n    };\n";
         return t.str();
-    };
-    auto vin_store = [&]() {
+}
+
+std::string BodyWriter::vin_store()
+{
         std::ostringstream t;
         for (size_t i = 0; i < out.inputs.size(); ++i) {
             const InputInfo& in = out.inputs[i];
@@ -4284,56 +4426,30 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                 t << "        if (c.ev_cur != c.ev_cur0) og::st_f(A, c, " << in.state_word << ", vin_" << i << ");\n";
         }
         return t.str();
-    };
-    // frames per straight-line scheduling region of the ordinary kernel's quiet-chunk loop.  A large graph with
-    // envelopes has three copies of the chunk body (no stage-end checks / no release arithmetic) and sits at the
-    // 128-VGPR cap: unrolling by two spills ~20 registers there (fm_voice: 2-4% slower at >= 131 072 voices, where
-    // this kernel runs); small graphs gain from it (4x saturator +5%).
-    int graph_weight = 0;
-    bool has_env = false;
-    for (int ni : order) {
-        graph_weight += node_weight(cg.nodes[ni].decl->type);
-        has_env = has_env || cg.nodes[ni].decl->type.rfind("AdsrEnvelope::", 0) == 0;
-    }
-    out.valu_estimate = graph_weight + 8; // + the mix bus
-    int unroll = (has_env && graph_weight >= 100) ? 1 : 2;
-    // Round 6: the whole 16-frame bus chunk as ONE straight-line region wherever registers allow.  A value that lives across
-    // frames -- the saturator's four half-band histories (62 live samples that shift every frame), phases, filter states --
-    // crosses the loop's back edge once per trip and has to sit where the loop head expects it: with two frames per trip the
-    // histories were copied on every trip (20 v_mov per frame of 162 VALU); with sixteen a sample is written straight into the
-    // register it will be read from a chunk later.  Interleaved A/B on one MI355X (profiles/r06_handoff_ab.md, r07f / r07g):
-    // SatGraph_4x 131 072 voices 3.33e11 -> 3.50 / 3.61 / 3.71e11 at 4 / 8 / 16; fm_voice 262 144 6.88e11 -> 6.97 / 6.92 /
-    // 7.02e11, 1 048 576 8.06e11 -> 8.17 / 8.06 / 8.17e11; osc+env+TPT 1.125e12 -> 1.157 / 1.161 / 1.153e12; the delay-line
-    // voice 5.21e11 -> 5.32 / 5.28 / 5.17e11 (its chunk is bracketed by the ring staging: four frames per trip); the
-    // electric piano does not move (its harmonics are not shifted) and keeps its two.  (The pipelined shapes always
-    // unrolled their chunks.)
-    if (unroll > 1) {
-        if (out.lpv > 1) unroll = 2;
-        else if (!out.rings.empty()) unroll = 4;
-        else if (!out.players.empty()) unroll = 16; // (a tick shifts the chunk's staged frames down: renames in a straight-line chunk)
-        else if (cg.N > 1) unroll = 16;
-        else unroll = (has_env && graph_weight >= 70) ? 4 : 8; // (fm_voice: sixteen is worth +0.7 % over four and brings spills into the tapped variants' chunk bodies)
-    }
-    if (const char* u = ogabi::experiment_knob("OGC_UNROLL")) unroll = std::max(1, std::min(16, atoi(u)));
+}
 
-    // A kernel is assembled from GROUPS of consecutive stages, one wave per group: the ordinary kernel
-    // has the single group {0..n-1}, the pipelined ones two or four groups.
-    const int NS = cg.n_stages;
-    auto cat = [&](const std::vector<int>& st, std::ostringstream Codegen::Sect::*m) {
+// A kernel is assembled from GROUPS of consecutive stages, one wave per group: the ordinary kernel
+// has the single group {0..n-1}, the pipelined ones two or four groups.
+std::string BodyWriter::cat(const std::vector<int>& st, std::ostringstream Codegen::Sect::*m)
+{
         std::string r;
         for (int k : st) r += (cg.sec[k].*m).str();
         return r;
-    };
-    // group index of a stage under a grouping
-    auto group_of = [](const std::vector<std::vector<int>>& groups, int stage) {
+}
+
+// group index of a stage under a grouping
+int BodyWriter::group_of(const std::vector<std::vector<int>>& groups, int stage)
+{
         for (size_t gi = 0; gi < groups.size(); ++gi)
             for (int k : groups[gi])
                 if (k == stage) return (int)gi;
         return -1;
-    };
-    // per-frame code of one group: stage code in order; a value read by a later stage is aliased right
-    // after its producer (same wave) or travels through its LDS channel (other wave)
-    auto group_tick = [&](const std::vector<std::vector<int>>& groups, int gi) {
+}
+
+// per-frame code of one group: stage code in order; a value read by a later stage is aliased right
+// after its producer (same wave) or travels through its LDS channel (other wave)
+std::string BodyWriter::group_tick(const std::vector<std::vector<int>>& groups, int gi)
+{
         std::ostringstream t;
         const std::vector<int>& st = groups[gi];
         for (size_t k = 0; k < cg.xvals.size(); ++k) {
@@ -4356,12 +4472,43 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
             }
         }
         return t.str();
-    };
-    std::vector<int> all_stages;
-    for (int k = 0; k < NS; ++k) all_stages.push_back(k);
+}
 
-    // ---- ordinary kernel: one wave = 64 voices, the whole node sequence -------------------------
-    std::ostringstream body;
+// min over the countdowns of a group's envelopes, or "" when it has none
+// (dynamic_events: a gate from another node can start a Release or a new stage on any frame)
+std::string BodyWriter::min_cnt(const std::vector<int>& st)
+{
+        std::string m;
+        if (!chunk_chk) return m;
+        for (int k : st)
+            for (const auto& cexp : cg.sec[k].env_cnts) m = m.empty() ? cexp : "min(" + m + ", " + cexp + ")";
+        return m;
+}
+
+std::string BodyWriter::rs_sum(const std::vector<int>& st)
+{
+        std::string m;
+        for (int k : st)
+            for (const auto& r : cg.sec[k].env_rs) m = m.empty() ? r : "(" + m + " + " + r + ")";
+        return m;
+}
+
+// `<E>.fc = (float)<E>.cnt;` for the envelopes of a group: in front of every loop whose ticks run the release arithmetic
+// (the release-free chunk variant steps cnt only), see og::Adsr::fc
+std::string BodyWriter::fc_sync(const std::vector<int>& st, const std::string& ind)
+{
+        std::string r;
+        for (int k : st)
+            for (const auto& cexp : cg.sec[k].env_cnts) {
+                const std::string E = cexp.substr(0, cexp.size() - 4); // "<E>.cnt"
+                r += ind + E + ".fc = (float)" + E + ".cnt;\n";
+            }
+        return r;
+}
+
+// ---- ordinary kernel: one wave = 64 voices, the whole node sequence -------------------------
+void BodyWriter::write_ordinary_kernel()
+{
     body << "template <bool RAMPS, bool TAPS>\n"
          << "__device__ __forceinline__ void voice_block(const OgBlockArgs& A)\n{\n"
          << "    __shared__ og::" << (out.voice_channels > 1 ? "BusLdsN<" + std::to_string(out.voice_channels) + ">" : std::string("BusLds")) << " bus;\n"
@@ -4380,33 +4527,6 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
                             // where it would also sit out the delay-line loads staged for the next chunk
         body << "    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)\n";
     // one frame of the voice graph (nodes in topological order); returns the voice's output sample
-    // min over the countdowns of a group's envelopes, or "" when it has none
-    // (dynamic_events: a gate from another node can start a Release or a new stage on any frame)
-    const bool chunk_chk = !(ogabi::experiment_knob("OGC_CHUNK_CHK") && atoi(ogabi::experiment_knob("OGC_CHUNK_CHK")) == 0) && !cg.dynamic_events;
-    auto min_cnt = [&](const std::vector<int>& st) {
-        std::string m;
-        if (!chunk_chk) return m;
-        for (int k : st)
-            for (const auto& cexp : cg.sec[k].env_cnts) m = m.empty() ? cexp : "min(" + m + ", " + cexp + ")";
-        return m;
-    };
-    auto rs_sum = [&](const std::vector<int>& st) {
-        std::string m;
-        for (int k : st)
-            for (const auto& r : cg.sec[k].env_rs) m = m.empty() ? r : "(" + m + " + " + r + ")";
-        return m;
-    };
-    // `<E>.fc = (float)<E>.cnt;` for the envelopes of a group: in front of every loop whose ticks run the release arithmetic
-    // (the release-free chunk variant steps cnt only), see og::Adsr::fc
-    auto fc_sync = [&](const std::vector<int>& st, const std::string& ind) {
-        std::string r;
-        for (int k : st)
-            for (const auto& cexp : cg.sec[k].env_cnts) {
-                const std::string E = cexp.substr(0, cexp.size() - 4); // "<E>.cnt"
-                r += ind + E + ".fc = (float)" + E + ".cnt;\n";
-            }
-        return r;
-    };
     body << "    auto tick = [&](const uint32_t f, auto chk) __attribute__((always_inline)) -> " << (out.voice_channels > 1 ? "og::OutN<" + std::to_string(out.voice_channels) + ">" : std::string("float")) << " {\n"
          << group_tick({all_stages}, 0);
     if (cg.frame_end.str().empty()) {
@@ -4491,490 +4611,638 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
          << cat(all_stages, &Codegen::Sect::pre_store) << "    if (c.valid) {\n"
          << cat(all_stages, &Codegen::Sect::store) << vin_store();
     body << "    }\n    og::voice_end(A, c);\n}\n";
+}
 
-    // ---- pipelined kernels: workgroup = K waves over the same 64 voices ----------------------------
-    // All waves take the same n_chunks + K - 1 steps, one barrier per step; at step t the wave of group
-    // s works on hand-off chunk t - s.  A value produced by group a and read by group b lives in an LDS
-    // ring of b - a + 1 chunks.  Which wave of the workgroup takes which group rotates with the
-    // workgroup index, so that the SIMDs of a CU do not each collect one kind of stage.
-    auto emit_pipeline = [&](const std::vector<std::vector<int>>& groups, int tag) {
-        const int K = (int)groups.size();
-        body << "\n// " << K << "-wave pipeline over the same 64 voices (small banks: more waves per SIMD).\n";
-        for (int gi = 0; gi < K; ++gi) {
-            body << "//   wave " << gi << ":";
-            for (int ni : order)
-                if (group_of(groups, cg.stage_of[ni]) == gi) body << " " << g.nodes[ni].name;
-            body << (gi == K - 1 ? " + the mix bus\n" : "\n");
-        }
-        // FD_T = 0: one workgroup barrier per hand-off (every wave one chunk behind its predecessor); FD_T >= 2: flag
-        // hand-off (og_kernel_rt.hip.h, handoff_wait / handoff_publish) over rings of FD_T chunks per crossing value
-        body << "template <bool RAMPS, bool TAPS, uint32_t XCH_T = 0, uint32_t FD_T = 0>\n"
-             << "__device__ __forceinline__ void voice_block_p" << tag << "(const OgBlockArgs& A)\n{\n"
-             << "    __shared__ og::" << (out.voice_channels > 1 ? "BusLdsN<" + std::to_string(out.voice_channels) + ">" : std::string("BusLds")) << " bus;\n";
-        {
-            // frames per hand-off: 8.  16 (OGC_XCH16, two-wave pipeline only) measured +2% on a 94-block run at
-            // 65 536 voices but -1.5% on the 188-block default run, and its doubled LDS rings leave room for only
-            // four workgroups per CU: 98 304 voices (six per CU) ran 29% slower.  4 is 11% slower.
-            size_t slots = 0;
-            for (const auto& xv : cg.xvals) {
-                int far = group_of(groups, xv.from);
-                for (int u : xv.users) far = std::max(far, group_of(groups, u));
-                const int depth = far - group_of(groups, xv.from) + 1;
-                if (depth > 1) slots += (size_t)depth;
-            }
-            const bool wide = K == 2 && slots * 16 * 64 * 4 <= 36 * 1024 && ogabi::experiment_knob("OGC_XCH16");
-            int xch = wide ? 16 : 8;
-            // OGC_XCH=4|16: experiment for the next round -- with the sticky chunk loops a hand-off costs ~9 VALU + ~17 SALU
-            // and a barrier instead of ~45 + ~40, so the trade between hand-off overhead (longer chunks) and lock-step wait /
-            // LDS footprint (shorter ones) has moved since the measurements above.  OG_BUS_CHUNK (16) must stay a multiple.
-            if (const char* ex = ogabi::experiment_knob("OGC_XCH")) {
-                const int want = atoi(ex);
-                if ((want == 4 || want == 8 || want == 16) && slots * (size_t)want * 64 * 4 <= 60 * 1024) xch = want;
-            }
-            // Round 5: the four-wave kernel waits more than it issues (54 % of its wave cycles), and 16-frame hand-offs -- half
-            // the barriers -- measured +2.4 % at the driver's command and +3.3 % on 94-block regions at 65 536 voices; but
-            // their LDS rings (fm_voice: 36.9 KB per workgroup) fit only four workgroups per CU, so a bank of five or six per
-            // CU would run in two rounds.  Both exist: XCH_T = 16 instantiates the wide form (og_k4w_*), which the engine
-            // launches when every workgroup of the bank is resident at once (og_engine.cpp, depth model).
-            body << "    constexpr uint32_t XCH = XCH_T ? XCH_T : " << xch << "u; // frames per hand-off between the waves\n";
-            if (K == 4 && xch == 8 && slots * 16 * 64 * 4 + 4160 * (size_t)std::max(1u, out.voice_channels) <= 40 * 1024) out.wide4 = true;
-        }
-        for (size_t k = 0; k < cg.xvals.size(); ++k) {
-            const auto& xv = cg.xvals[k];
-            int far = group_of(groups, xv.from);
-            for (int u : xv.users) far = std::max(far, group_of(groups, u));
-            const int depth = far - group_of(groups, xv.from) + 1;
-            body << "    constexpr uint32_t XD" << k << " = " << (depth > 1 ? "FD_T ? FD_T : " : "") << depth << ";\n";
-            if (depth > 1) body << "    __shared__ float chan" << k << "[XD" << k << "][XCH][OG_WAVE];\n";
-        }
-        body << "    __shared__ uint32_t prog[" << K << "]; // flag hand-off: chunks completed, per stage\n"
-             << "    __shared__ uint32_t cons[" << K << "]; // ... and chunks whose inputs this stage has taken out of the rings\n"
-             << "    if constexpr (FD_T != 0) {\n"
-             << "        if (threadIdx.x < " << K << "u) prog[threadIdx.x] = cons[threadIdx.x] = 0u;\n"
-             << "        __syncthreads();\n"
-             << "    }\n";
-        const char* rot_expr[5] = {"0u", "blockIdx.x", "(blockIdx.x >> 3)", "(blockIdx.x >> 5)", "(blockIdx.x >> 8)"};
-        int rot = 1;
-        if (const char* er = ogabi::experiment_knob("OGC_ROT")) rot = std::max(0, std::min(4, atoi(er)));
-        body << "    const uint32_t stage = (threadIdx.x / OG_WAVE + " << rot_expr[rot] << ") % " << K << "u;\n"
-             << "    og::VoiceCtx c;\n"
-             << "    og::voice_begin_split<TAPS>(A, c);\n"
-             << cg.common_decl.str() << "    if (c.valid) {\n" << cg.common_load.str() << "    }\n"
-             << "    const uint32_t n_chunks = (A.frames + XCH - 1) / XCH;\n";
-        for (int gi = 0; gi < K; ++gi) {
-            const std::vector<int>& st = groups[gi];
-            const bool last = gi == K - 1;
-            int base_prio = 0;
-            body << (gi == 0 ? "    if (stage == 0) {\n" : "    } else if (stage == " + std::to_string(gi) + ") {\n");
-            {
-                // VALU issue on a SIMD is arbitrated by priority, then age (MI355X_MICROARCH.md).  The first wave of
-                // the pipeline (the light producer: envelopes, first operator) runs at priority 1: it never becomes
-                // the straggler its consumers wait for at the hand-off barrier.  Measured, fm_voice: two waves at
-                // 65 536 voices 0.0741 -> 0.0660 ms; four waves at 32 768 voices 0.0500 -> 0.0484 ms; raising the
-                // other waves as well (2,1 / 3,2,1,0) is no better.  OGC_PRIO="p0,p1[,p2,p3]" overrides.
-                // Round 4, four waves (depth-first order): the LAST wave (filter, bus) lowest, the first highest, the middle
-                // ones between -- 2,1,1,0.  Interleaved A/B at the driver's command, 65 536 voices: 1,0,0,0 3.08e11; 0,0,0,0
-                // 3.00e11; 0,0,1,0 3.20e11; 1,1,1,0 3.16e11; 2,1,1,0 3.26e11; 3,2,1,0 3.27e11; 3,2,2,0 3.28e11; 2,1,2,0 3.28e11;
-                // 3,2,1,1 3.14e11 -- whatever is upstream must not wait for the wave that closes the chunk; the exact levels
-                // above it are within noise.  (Neutral on the 188-block run, +1 % at 32 768 and 131 072 voices.)
-                std::vector<int> pr = K >= 3 ? std::vector<int>{2, 1, 1, 0} : std::vector<int>{1, 0, 0, 0};
-                if (K >= 3) {
-                    pr.assign((size_t)K, 1);
-                    pr.front() = 2;
-                    pr.back() = 0;
-                }
-                if (const char* ep = ogabi::experiment_knob("OGC_PRIO")) {
-                    pr.clear();
-                    for (const char* q = ep; *q; ++q)
-                        if (isdigit((unsigned char)*q)) pr.push_back(*q - '0');
-                }
-                base_prio = gi < (int)pr.size() ? pr[gi] : 0;
-                // Round 6, flag hand-off (FD_T != 0): the order turns round -- 0,1,2,3, downstream first.  Without the barrier a
-                // consumer that has its inputs runs them down at once and the producers fill in behind it; the rings stay near
-                // empty and no wave sits blocked on a full one.  Interleaved A/B, 65 536 voices, 16-frame chunks, rings of 2
-                // (profiles/r06_handoff_ab.md): barrier 2,1,1,0 (round 5) 5.45e11 at the driver's command; flags 2,1,1,0
-                // 5.56e11; flags 0,0,0,0 5.40e11; flags 0,1,1,2 5.65e11; 0,0,1,2 5.74e11; 0,1,2,2 5.57e11; 1,1,2,3 5.38e11;
-                // 0,0,2,3 5.32e11; flags 0,1,2,3 5.93e11 -- and the barrier with 0,1,2,3 4.89e11: the order only works without
-                // the lock step.  Moving-cutoff variant 3.95e11 -> 4.37e11; 188-block regions 6.42e11 -> 6.2e11 (-3 %).
-                const int flag_prio = ogabi::experiment_knob("OGC_PRIO") ? base_prio : std::min(gi, 3);
-                body << "    constexpr int BASE_PRIO = FD_T != 0 ? " << flag_prio << " : " << base_prio << ";\n"
-                     << "    og::set_prio<BASE_PRIO>();\n";
-            }
-            body << cat(st, &Codegen::Sect::decl) << "    if (c.valid) {\n" << cat(st, &Codegen::Sect::load) << "    }\n";
-            body << "    auto derive = [&]() __attribute__((always_inline)) {\n" << cat(st, &Codegen::Sect::derive) << "    };\n";
-            body << cat(st, &Codegen::Sect::pre) << "    derive();\n";
-            // hand-off values this wave reads: fetched for the whole chunk before its first tick, so that the LDS
-            // latency is paid once per chunk and not in front of every frame's first dependent instruction
-            std::vector<size_t> reads;
-            for (size_t k = 0; k < cg.xvals.size(); ++k) {
-                const auto& xv = cg.xvals[k];
-                bool used_here = false;
-                for (int u : xv.users) used_here = used_here || group_of(groups, u) == gi;
-                if (used_here && group_of(groups, xv.from) != gi) reads.push_back(k);
-            }
-            for (size_t k : reads) body << "    float xp" << k << "[XCH];\n";
-            // Release reciprocals from a table (four-wave shapes; the sticky release loop below, wide form only, og::rcp_fetch):
-            // one 16-byte load per envelope and four frames instead of v_rcp_f32 + a subtraction per envelope and frame.
-            // OGC_RCP_TAB=0 keeps v_rcp_f32 in that loop (A/B).
-            std::vector<std::string> envs; // "<E>" of this wave's outer-rate envelopes
-            if (K == 4 && !(ogabi::experiment_knob("OGC_RCP_TAB") && atoi(ogabi::experiment_knob("OGC_RCP_TAB")) == 0))
-                for (int k : st)
-                    for (const auto& cexp : cg.sec[k].env_cnts) envs.push_back(cexp.substr(0, cexp.size() - 4)); // "<E>.cnt"
-            for (const auto& E : envs) body << "    float " << E << "_rcp[XCH];\n";
-            // Ramp-table rows (ramped inputs: the RAMPS variants; stream inputs: every variant).  `RV(row, slot)` / `ST(row)`
-            // read A.ramp_table[row * stride + f] -- a scalar load behind a 64-bit address computation, per input and frame:
-            // the launches that read the table took 1.8x the time of the others (SALU 2.9x per block, round 5 counters).  In
-            // the unrolled chunk bodies the rows this wave reads are fetched for the WHOLE chunk at its top, next to the
-            // hand-off values (consecutive words from a uniform base: wide scalar loads); the rolled event path keeps the
-            // direct read.  RV -> RVP / ST -> STP in this wave's tick text.
-            std::string tick_text = group_tick(groups, gi);
-            std::set<int> rows;
-            for (const char* mac : {"RV(", "ST("}) {
-                const std::string pre_mac = std::string(mac, 2) + "P(";
-                for (size_t pos = tick_text.find(mac); pos != std::string::npos; pos = tick_text.find(mac, pos + 1)) {
-                    if (pos > 0 && (isalnum((unsigned char)tick_text[pos - 1]) || tick_text[pos - 1] == '_')) continue;
-                    rows.insert(atoi(tick_text.c_str() + pos + 3));
-                    tick_text.replace(pos, 3, pre_mac);
-                }
-            }
-            for (int r : rows) body << "    float rv_" << r << "[XCH];\n";
-            for (const auto& E : envs) {
-                const std::string from = "og::adsr_tick<decltype(chk)::release, true>(" + E + ")";
-                const std::string to = "og::adsr_tick_chunk<decltype(chk)::release, decltype(chk)::table>(" + E + ", " + E + "_rcp, j)";
-                const size_t pos = tick_text.find(from);
-                if (pos == std::string::npos) throw std::runtime_error("internal: no tick of " + E + " in its wave");
-                tick_text.replace(pos, from.size(), to);
-            }
-            body << "    auto tick = [&](const uint32_t f, const uint32_t ch, const uint32_t j, auto chk) __attribute__((always_inline))"
-                 << (last ? (out.voice_channels > 1 ? " -> og::OutN<" + std::to_string(out.voice_channels) + ">" : std::string(" -> float")) : std::string()) << " {\n"
-                 << tick_text;
-            if (last) body << "        return " << bus_expr << ";\n";
-            body << "    };\n";
-            body << events_code(st);
-            // SALU instructions cost issue slots like VALU ones: the quiet chunk is a straight-line,
-            // fully unrolled body; per-frame tests only exist on the (rare) event path
-            auto call = [&](const std::string& flag) {
-                const std::string t = std::string("tick(f, ch, j, og::BoolC<") + flag + ">{})";
-                // row of the bus tile: f % OG_BUS_CHUNK = (base % OG_BUS_CHUNK) + j -- `base` is a multiple of XCH, which divides
-                // OG_BUS_CHUNK, so there is no carry; written this way the chunk-invariant part is formed once per chunk and the
-                // eight stores of the unrolled body take immediate offsets (one v_add + two SALU per frame less in the bus wave)
-                return last ? "og::bus_put<TAPS>(A, c, bus, f, (base & (OG_BUS_CHUNK - 1u)) + j, " + t + ");" : t + ";";
-            };
-            // node steady-state conditions of this wave's stages (Sect::fast_conds), as in the ordinary kernel
-            std::string steady;
-            for (int k : st)
-                for (const auto& fc : cg.sec[k].fast_conds) steady += (steady.empty() ? "" : " && ") + fc;
-            // flags: stage-end checks, release arithmetic, hand-off values prefetched, node steady states
-            // `stay` (sticky chunks): the condition -- on the NEXT chunk, `base1` -- under which this very variant runs again.
-            // The wave then stays in a loop of its own around the variant's body (hand-off barrier inside) instead of
-            // going back through the chunk loop's head.  Why: the chunk loop merges four bodies (two quiet variants, the
-            // checked one, the rolled one) and the compiler brings every loop-carried value (envelope, phases, event
-            // cursor: ~20 registers) back to one place after each of them -- 30 v_mov + ~40 SALU per wave and chunk, a sixth
-            // of a quiet chunk's instructions (scripts/isa_blocks.py).  A loop with ONE body keeps its values where they are.
-            // Static count, fm_voice four-wave kernel, release-free quiet chunk of waves 0-2: 231 + 230 + 222 -> ~201 + 187 + 194
-            // VALU per 8 frames; rocprofv3 SQ_INSTS_VALU per 64-voice frame at the driver's command 120.7 -> 107.4.  Interleaved A/B on one MI355X, 65 536 voices: 94-block
-            // runs 3.73e11 -> 4.01e11, the driver's command 3.29e11 -> 3.54e11, 131 072 voices 3.90e11 -> 4.20e11 (+7.5 % each);
-            // parity subset of the GPU suite green with the variant before it became the default.  OGC_STICKY=0 turns it off.
-            const bool sticky = !(ogabi::experiment_knob("OGC_STICKY") && atoi(ogabi::experiment_knob("OGC_STICKY")) == 0) && !ogabi::experiment_knob("OGC_FORCE_PATH");
-            std::string stay_path; // conditions of the enclosing branches, on the next chunk
-            // hand-off partners of this wave: the stages whose values it reads (producers) and the stages that read its values
-            std::set<int> producers, consumers;
-            for (const auto& xv : cg.xvals) {
-                const int from = group_of(groups, xv.from);
-                for (int u : xv.users) {
-                    const int to = group_of(groups, u);
-                    if (to == from) continue;
-                    if (to == gi) producers.insert(from);
-                    if (from == gi) consumers.insert(to);
-                }
-            }
-            for (int q : producers) body << "    uint32_t seen_p" << q << " = 0u;\n";
-            for (int q : consumers) body << "    uint32_t seen_c" << q << " = 0u;\n";
-            // flags: before chunk `ch` -- its inputs are complete, and the ring slots it writes have been read
-            std::string wait_all = "if constexpr (FD_T != 0) {";
-            for (int q : producers) wait_all += " og::handoff_wait(&prog[" + std::to_string(q) + "], seen_p" + std::to_string(q) + ", ch + 1u);";
-            for (int q : consumers) wait_all += " og::handoff_wait(&cons[" + std::to_string(q) + "], seen_c" + std::to_string(q) + ", ch + 1u - FD_T);";
-            wait_all += " }";
-            // (a stage that reads hand-off values gives their ring slots back as soon as the chunk's values sit in its registers --
-            //  `taken`, after the prefetch of the unrolled bodies -- or, on the rolled path, with the chunk)
-            const std::string taken = producers.empty() ? std::string()
-                                                        : "if constexpr (FD_T != 0) og::handoff_publish(&cons[" + std::to_string(gi) + "], ch + 1u);";
-            const std::string sync_line = "if constexpr (FD_T != 0) { og::handoff_publish(&prog[" + std::to_string(gi) + "], ch + 1u);" +
-                                          (producers.empty() ? std::string() : " __hip_atomic_store(&cons[" + std::to_string(gi) + "], ch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);") +
-                                          " } else OG_HANDOFF_BARRIER(); // hand-off: chunk `ch` of this stage is complete";
-            const std::string bus_tail_fmt = // %B = first frame of the finished chunk, %N = its length
-                "{ // the bus tile holds OG_BUS_CHUNK frames = OG_BUS_CHUNK / XCH hand-offs\n"
-                "%I    const uint32_t lastf = %B + %N - 1;\n"
-                "%I    if ((lastf % OG_BUS_CHUNK) == OG_BUS_CHUNK - 1 || lastf + 1 == A.frames)\n"
-                "%I        og::bus_chunk_reduce(A, c, bus, lastf - (lastf % OG_BUS_CHUNK), (lastf % OG_BUS_CHUNK) + 1);\n"
-                "%I}\n";
-            auto bus_tail = [&](const std::string& ind, const std::string& n_expr) {
-                std::string o = ind + bus_tail_fmt;
-                auto sub = [&](const std::string& k, const std::string& v) {
-                    for (size_t q = o.find(k); q != std::string::npos; q = o.find(k, q + v.size())) o.replace(q, k.size(), v);
-                };
-                sub("%I", ind);
-                sub("%B", "base");
-                sub("%N", n_expr);
-                return o;
-            };
-            auto row_fetch = [&](const std::string& ind) { // the table rows of this chunk (`base` = its first frame within the launch)
-                std::ostringstream o;
-                if (rows.empty()) return std::string();
-                bool only_ramps = true; // (ST rows -- stream inputs -- are read in every variant, RV rows only under RAMPS)
-                for (size_t pos = tick_text.find("STP("); pos != std::string::npos; pos = std::string::npos) only_ramps = false;
-                o << ind << (only_ramps ? "if (RAMPS) {\n" : "{\n");
-                for (int r : rows)
-                    o << ind << "    og::row_fetch<XCH>(rv_" << r << ", A.ramp_table + (size_t)" << r << " * A.ramp_stride + base);\n";
-                o << ind << "}\n";
-                return o.str();
-            };
-            // The quiet release loop of the four-wave form takes its reciprocals from the table in the wide instantiation
-            // (FD_T != 0; the 8-frame one keeps v_rcp_f32): one 16-byte load per envelope and four frames.  A wide launch whose
-            // releases the table does not cover (rcp_len = 0) sends chunks with a releasing lane to the checked body instead
-            // (`rel_ok` in the quiet test below).  Only where the checked body is the alternative (one_checked).
-            bool tab_ok = false;
-            auto quiet = [&](const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string()) {
-                const bool pre = !reads.empty() || !rows.empty();
-                const bool loop = sticky && !stay.empty();
-                const std::string ind = loop ? ind0 + "    " : ind0;
-                const bool tab = tab_ok && loop && !envs.empty() && std::string(chk_flag) == "false" && std::string(rel_flag) == "true";
-                if (tab) {
-                    body << ind0 << "if constexpr (FD_T != 0) { // the first chunk's release reciprocals\n";
-                    for (const auto& E : envs) body << ind0 << "    og::rcp_fetch<XCH>(" << E << "_rcp, A, " << E << ".cnt);\n";
-                    body << ind0 << "}\n";
-                }
-                if (loop) body << ind0 << "for (;;) { // sticky: this variant again while its conditions hold\n";
-                if (tab)
-                    for (const auto& E : envs) body << ind << "const uint32_t " << E << "_nx = " << E << ".cnt - XCH; // (at the next chunk's top)\n";
-                if (std::string(rel_flag) == "true") {
-                    if (tab) body << ind << "if constexpr (FD_T == 0) {\n" << fc_sync(st, ind + "    ") << ind << "}\n";
-                    else body << fc_sync(st, ind);
-                }
-                if (pre) {
-                    body << row_fetch(ind);
-                    body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
-                    for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
-                    body << ind << "}\n";
-                    if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
-                }
-                const std::string flag = std::string(chk_flag) + ", " + rel_flag + ", " + (pre ? "true" : "false") + ", " +
-                                         (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "");
-                body << ind << "#pragma unroll\n"
-                     << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
-                     << ind << "    const uint32_t f = base + j;\n"
-                     << ind << "    " << call(flag) << "\n";
-                // (the next chunk's four reciprocals go into the registers these frames have just read: nothing moves across the
-                //  back edge; a chunk the loop then leaves has loaded them for nothing, inside the table's padding)
-                if (tab) {
-                    body << ind << "    if constexpr (FD_T != 0) {\n";
-                    for (const auto& E : envs) body << ind << "        og::rcp_refill<XCH>(" << E << "_rcp, A, " << E << "_nx, j);\n";
-                    body << ind << "    }\n";
-                }
-                body << ind << "}\n";
-                if (loop) {
-                    body << ind << "const uint32_t ch1 = ch + 1u, base1 = base + XCH;\n"
-                         << ind << "if (!(ch1 < n_chunks && A.frames - base1 >= (uint32_t)XCH && " << stay_path << (stay == "1" ? "" : " && " + stay)
-                         << ")) break;\n";
-                    if (last) body << bus_tail(ind, "XCH");
-                    body << ind << sync_line << "\n"
-                         << ind << "++t;\n" << ind << "ch = ch1;\n" << ind << "base = base1;\n";
-                    if (!wait_all.empty()) body << ind << wait_all << "\n";
-                    body << ind0 << "}\n";
-                }
-            };
-            const std::string mc = min_cnt(st);
-            // ---- events in the pipelined kernels -----------------------------------------------------------------
-            // (1) A wave only has to leave the straight-line path for events IT handles.  Every wave of the pipeline
-            //     walks the voice's event list, but e.g. FMVoice's second wave (operators 2 and 1, filter) has no
-            //     handler for `gate` -- only the envelope wave has -- and used to run the chunk frame by frame for
-            //     nothing.  Events without a handler in this wave's stages are consumed at the top of the chunk.
-            // (2) A chunk that does hold an event (or an envelope stage end) runs the UNROLLED body with one
-            //     wave-uniform `any lane has an event on this frame` test per frame, instead of a rolled frame loop
-            //     that serialises the frames (measured: the rolled event chunk costs twice a quiet one, and the launch
-            //     ends with the wave that met the most events).  It replaces the stage-end-check variant of the quiet
-            //     chunk, so the kernel does not grow.
-            // Measured (scripts/dbg_event_cost.py, fm_voice, 65 536 voices, kernel ms per 256-frame block, round-2 form ->
-            // both): one retrigger per voice in 5 120 frames 0.0641 -> 0.0623, two 0.0714 -> 0.0677 (the cost of an
-            // event falls by a third, nearly all of it from (1)) -- but (2) inlines the handlers into every frame of the
-            // checked body (two-wave kernel 26.8 -> 35.9 KB) and the QUIET path pays for it: idle bank 0.0514 -> 0.0528,
-            // sustaining 0.0536 -> 0.0553.  At the benchmark's event density the two cancel (2.73e11 either way), so
-            // (1) was on and (2) off through round 3: OGC_EVSKIP=0 turns (1) off.
-            const bool ev_skip = !(ogabi::experiment_knob("OGC_EVSKIP") && atoi(ogabi::experiment_knob("OGC_EVSKIP")) == 0);
-            // (round 4: (2) is ON -- with the event records prefetched into registers (og::VoiceCtx::nx_*) the handlers inlined
-            //  into the checked body no longer carry loads and waits; four-wave kernel at 65 536 voices, interleaved A/B:
-            //  3.07e11 either way at the driver's command, 3.57e11 against 3.44e11 on the 188-block run; OGC_EVUNROLL=0 turns it off)
-            const bool ev_unroll = !(ogabi::experiment_knob("OGC_EVUNROLL") && atoi(ogabi::experiment_knob("OGC_EVUNROLL")) == 0);
-            std::string relevant; // condition on `tgt`: this wave has a handler for the event
-            {
-                const std::string code = cat(st, &Codegen::Sect::derive) + group_tick(groups, gi) + cat(st, &Codegen::Sect::decl);
-                for (size_t i = 0; i < out.inputs.size(); ++i) {
-                    const InputInfo& in = out.inputs[i];
-                    if (!(in.decl.kind == Kind::Value && in.decl.per_voice)) continue;
-                    const std::string var = "vin_" + std::to_string(i);
-                    bool used = false;
-                    for (size_t p = code.find(var); p != std::string::npos && !used; p = code.find(var, p + 1)) {
-                        const size_t e = p + var.size();
-                        used = e >= code.size() || !isdigit((unsigned char)code[e]);
-                    }
-                    // (the first wave stores the per-voice inputs back: it applies every SETVALUE)
-                    if (used || gi == 0) relevant += (relevant.empty() ? "" : " || ") + ("tgt == (OG_EV_SETVALUE | " + std::to_string(i) + "u)");
-                }
-                std::set<int> handled;
-                for (int k : st)
-                    for (auto& kv : cg.sec[k].ev_handlers)
-                        if (!kv.second.str().empty()) handled.insert(kv.first);
-                for (int h : handled) relevant += (relevant.empty() ? "" : " || ") + ("tgt == " + std::to_string(h) + "u");
-                if (relevant.empty()) relevant = "false";
-            }
-            const char* force = ogabi::experiment_knob("OGC_FORCE_PATH"); // experiment knob: b | c | ev -- quiet chunks take the release-arithmetic / stage-end-check / event path (results stay valid)
-            // the checked chunk: unrolled, stage-end checks and release arithmetic on, events applied on their frame
-            auto checked = [&](const std::string& ind) {
-                const bool pre = !reads.empty() || !rows.empty();
-                body << fc_sync(st, ind);
-                if (pre) {
-                    body << row_fetch(ind);
-                    body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
-                    for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
-                    body << ind << "}\n";
-                    if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
-                }
-                const std::string flag = std::string("true, true, ") + (pre ? "true" : "false") + ", false";
-                body << ind << "#pragma unroll\n"
-                     << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
-                     << ind << "    const uint32_t f = base + j;\n"
-                     << ind << "    if (__any((int)(f == c.next_ev))) events(f); // (wave-uniform: rare)\n"
-                     << ind << "    " << call(flag) << "\n"
-                     << ind << "}\n";
-            };
-            auto variants = [&](bool st_flag, const std::string& ind0) {
-                if (force && force[0] == 'c') {
-                    quiet("true", "true", st_flag, ind0);
-                } else if (mc.empty()) {
-                    quiet("true", "true", st_flag, ind0, "1");
-                } else {
-                    const std::string no_end = "__all((int)(" + mc + " > (uint32_t)XCH))", no_rel = "__all((int)(" + rs_sum(st) + " == 0.0f))";
-                    body << ind0 << "if (" << no_end << ") { // no envelope stage ends in this chunk\n"
-                         << ind0 << "    if (" << no_rel << ") { // ... and no lane is in Release\n";
-                    quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "        ", no_end + " && " + no_rel);
-                    body << ind0 << "    } else {\n";
-                    quiet("false", "true", st_flag, ind0 + "        ", no_end + " && !" + no_rel);
-                    body << ind0 << "    }\n" << ind0 << "} else {\n";
-                    quiet("true", "true", st_flag, ind0 + "    ");
-                    body << ind0 << "}\n";
-                }
-            };
-            // the two straight-line variants only (the caller has established that no countdown ends in the chunk)
-            const int rel_prio = ogabi::experiment_knob("OGC_RELPRIO") ? atoi(ogabi::experiment_knob("OGC_RELPRIO")) : -1;
-            auto fast_variants = [&](bool st_flag, const std::string& ind0) {
-                const std::string no_rel = "__all((int)(" + rs_sum(st) + " == 0.0f))";
-                body << ind0 << "if (" << no_rel << ") { // no lane is in Release\n";
-                quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "    ", no_rel);
-                body << ind0 << "} else {\n";
-                // OGC_RELPRIO=n (experiment for grouped banks, og_group_voices: the waves that release are then few and
-                // whole, and their workgroups are the ones a launch waits for; measured WITHOUT grouping in round 4: loses)
-                if (rel_prio >= 0) body << ind0 << "    __builtin_amdgcn_s_setprio(" << rel_prio << ");\n";
-                quiet("false", "true", st_flag, ind0 + "    ", "!" + no_rel);
-                if (rel_prio >= 0) body << ind0 << "    og::set_prio<BASE_PRIO>();\n";
-                body << ind0 << "}\n";
-            };
-            if (last) body << "    og::bus_init(c, bus); // (this wave owns the tile)\n";
-            body << "    for (uint32_t t = 0; t < n_chunks + (FD_T ? 0u : " << (K - 1) << "u); ++t) {\n"
-                 << "        " << (sticky ? "" : "const ") << "uint32_t ch = t - (FD_T ? 0u : " << gi << "u);\n"
-                 << "        if (ch < n_chunks) {\n";
-            if (!wait_all.empty()) body << "        " << wait_all << "\n";
-            body
-                 << "        " << (sticky ? "" : "const ") << "uint32_t base = ch * XCH;\n"
-                 << "        const uint32_t n = min((uint32_t)XCH, A.frames - base);\n";
-            if (ev_skip && relevant != "true")
-                body << "        if (!__all((int)(c.next_ev >= base + XCH))) { // consume the events this wave has no handler for\n"
-                     << "            while (c.next_ev < base + XCH) {\n"
-                     << "                const uint32_t tgt = c.nx_target;\n"
-                     << "                if (" << relevant << ") break;\n"
-                     << "                og::ev_advance(A, c);\n"
-                     << "            }\n"
-                     << "        }\n";
-            // A wave that meets an event or an envelope stage end runs the checked body for that chunk -- about twice the
-            // work of a quiet one -- and the other waves of its workgroup wait for it at the hand-off barrier: it runs
-            // that chunk at the highest priority and drops back afterwards.  Interleaved A/B, fm_voice, 65 536 voices,
-            // 94-block runs, nine pairs: +0.9 .. +5.8 %, mean +2.1 % (3.68e11 -> 3.76e11); level 2 instead of 3 gives a
-            // third of it; neutral at 32 768 and 262 144 voices; raising the release-arithmetic variant as well loses
-            // the gain.  (The two-wave kernel carries it too although it does nothing for it -- forced with
-            // OSCEN_GPU_SPLIT=2 at 65 536 voices: 3.16e11 with, 3.19e11 without; the engine does not pick that kernel at
-            // any bank size of the bench.)  OGC_SLOWPRIO=-1 turns it off.
-            const int slow_prio = ogabi::experiment_knob("OGC_SLOWPRIO") ? atoi(ogabi::experiment_knob("OGC_SLOWPRIO")) : 3;
-            const bool one_checked = ev_unroll && !mc.empty() && !force; // events and stage ends share ONE unrolled, checked body
-            tab_ok = one_checked && !envs.empty();
-            const std::string rel_ok = tab_ok ? " && (FD_T == 0 || A.rcp_len != 0u || __all((int)(" + rs_sum(st) + " == 0.0f)))" : std::string();
-            if (one_checked)
-                body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH)) && __all((int)(" << mc
-                     << " > (uint32_t)XCH))" << rel_ok << ") { // nothing happens in this chunk: no event, no envelope stage end\n";
-            else
-                body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH))" << (force && force[0] == 'e' ? " && A.frames == 0u" : "") << ") {\n";
-            auto pick = [&](bool st_flag, const std::string& ind) {
-                if (one_checked) fast_variants(st_flag, ind);
-                else variants(st_flag, ind);
-            };
-            const std::string stay_entry = std::string("__all((int)(c.next_ev >= base1 + XCH))") +
-                                           (one_checked ? " && __all((int)(" + mc + " > (uint32_t)XCH))" : std::string());
-            if (steady.empty()) {
-                stay_path = stay_entry;
-                pick(false, "            ");
-            } else {
-                const std::string all_steady = "__all((int)(!c.valid || (" + steady + ")))";
-                body << "            constexpr uint32_t CHUNK = XCH;\n"
-                     << "            if (" << all_steady << ") { // node steady states hold for the whole chunk\n";
-                stay_path = stay_entry + " && " + all_steady;
-                pick(true, "                ");
-                body << "            } else {\n";
-                stay_path = stay_entry + " && !" + all_steady;
-                pick(false, "                ");
-                body << "            }\n";
-            }
-            if (one_checked && ogabi::experiment_knob("OGC_STAGEEND_BODY") && atoi(ogabi::experiment_knob("OGC_STAGEEND_BODY")) != 0) {
-                // experiment (round 6): a chunk with a stage end but NO event takes a body with the stage-end checks and without
-                // the per-frame event tests and the inlined handlers
-                body << "        } else if (n == XCH && __all((int)(c.next_ev >= base + XCH))) { // a stage end, no event\n";
-                if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << ");\n";
-                quiet("true", "true", false, "            ");
-                if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
-            }
-            if (one_checked) {
-                body << "        } else if (n == XCH) { // an event or a stage end in this chunk: the checked, unrolled body\n";
-                if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << "); // the wave on the slow path is the straggler\n";
-                checked("            ");
-                if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
-            }
-            body << "        } else {\n"
-                 << fc_sync(st, "            ")
-                 << "            for (uint32_t j = 0; j < n; ++j) {\n"
-                 << "                const uint32_t f = base + j;\n"
-                 << "                events(f);\n"
-                 << "                " << call("true") << "\n"
-                 << "            }\n"
-                 << "        }\n";
-            if (last) body << bus_tail("        ", "n");
-            body << "        }\n"
-                 << "        " << sync_line << "\n"
-                 << "    }\n";
-            if (last) body << "    og::bus_flush(A, c, bus);\n";
-            body << cat(st, &Codegen::Sect::pre_store) << "    if (c.valid) {\n" << cat(st, &Codegen::Sect::store)
-                 << (gi == 0 ? vin_store() : std::string()) << "    }\n";
-            if (gi == 0) body << "    og::voice_end(A, c);\n";
-        }
-        body << "    }\n}\n";
-    };
-    if (!cg.groups2.empty()) emit_pipeline(cg.groups2, 2);
-    if (!cg.groups4.empty()) emit_pipeline(cg.groups4, 4);
+// One wave (group of stages) of a pipelined kernel: what its prologue works out and its chunk-loop variants share.
+struct PipelineWave {
+    BodyWriter& bw;
+    std::ostringstream& body;
+    Codegen& cg;
+    CompiledGraph& out;
+    const std::vector<std::vector<int>>& groups;
+    const int K, gi;
+    const std::vector<int>& st;
+    const bool last;
+    std::vector<size_t> reads;     // hand-off values this wave reads (indices into cg.xvals)
+    std::vector<std::string> envs; // "<E>" of this wave's outer-rate envelopes
+    std::set<int> rows;            // ramp-table rows its tick reads
+    std::string tick_text, steady, mc;
+    bool sticky = true;
+    std::string stay_path; // conditions of the enclosing branches, on the next chunk
+    std::set<int> producers, consumers;
+    std::string wait_all, taken, sync_line;
+    bool tab_ok = false;
+    const char* force = nullptr;
+    int rel_prio = -1;
 
-    std::string user_src;
-    for (const auto& kv : cg.user_fns) user_src += kv.second;
-    const std::string body_s = user_src + body.str();
-    if (zero_nodes) {
-        *zero_body = body_s;
-        return cgp;
+    PipelineWave(BodyWriter& w, const std::vector<std::vector<int>>& gr, int group)
+        : bw(w), body(w.body), cg(w.cg), out(w.out), groups(gr), K((int)gr.size()), gi(group), st(gr[(size_t)group]), last(group == K - 1)
+    {
     }
-    // ZeroChains (above): the Gain / AddValue nodes and the slots the engine tests
+    void prologue();
+    void handoff_setup();
+    void chunk_loop();
+    void epilogue();
+    std::string call(const std::string& flag) const;
+    std::string bus_tail(const std::string& ind, const std::string& n_expr) const;
+    std::string row_fetch(const std::string& ind) const;
+    void quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string());
+    void checked(const std::string& ind);
+    void variants(bool st_flag, const std::string& ind0);
+    void fast_variants(bool st_flag, const std::string& ind0);
+};
+
+// the hand-off length, the LDS rings of the values that cross between the waves and the flags of the flag hand-off
+void BodyWriter::pipeline_lds(const std::vector<std::vector<int>>& groups)
+{
+    const int K = (int)groups.size();
+    // frames per hand-off: 8.  16 (OGC_XCH16, two-wave pipeline only) measured +2% on a 94-block run at
+    // 65 536 voices but -1.5% on the 188-block default run, and its doubled LDS rings leave room for only
+    // four workgroups per CU: 98 304 voices (six per CU) ran 29% slower.  4 is 11% slower.
+    size_t slots = 0;
+    for (const auto& xv : cg.xvals) {
+        int far = group_of(groups, xv.from);
+        for (int u : xv.users) far = std::max(far, group_of(groups, u));
+        const int depth = far - group_of(groups, xv.from) + 1;
+        if (depth > 1) slots += (size_t)depth;
+    }
+    const bool wide = K == 2 && slots * 16 * 64 * 4 <= 36 * 1024 && ogabi::experiment_knob("OGC_XCH16");
+    int xch = wide ? 16 : 8;
+    // OGC_XCH=4|16: experiment for the next round -- with the sticky chunk loops a hand-off costs ~9 VALU + ~17 SALU
+    // and a barrier instead of ~45 + ~40, so the trade between hand-off overhead (longer chunks) and lock-step wait /
+    // LDS footprint (shorter ones) has moved since the measurements above.  OG_BUS_CHUNK (16) must stay a multiple.
+    if (const char* ex = ogabi::experiment_knob("OGC_XCH")) {
+        const int want = atoi(ex);
+        if ((want == 4 || want == 8 || want == 16) && slots * (size_t)want * 64 * 4 <= 60 * 1024) xch = want;
+    }
+    // Round 5: the four-wave kernel waits more than it issues (54 % of its wave cycles), and 16-frame hand-offs -- half
+    // the barriers -- measured +2.4 % at the driver's command and +3.3 % on 94-block regions at 65 536 voices; but
+    // their LDS rings (fm_voice: 36.9 KB per workgroup) fit only four workgroups per CU, so a bank of five or six per
+    // CU would run in two rounds.  Both exist: XCH_T = 16 instantiates the wide form (og_k4w_*), which the engine
+    // launches when every workgroup of the bank is resident at once (og_engine.cpp, depth model).
+    body << "    constexpr uint32_t XCH = XCH_T ? XCH_T : " << xch << "u; // frames per hand-off between the waves\n";
+    if (K == 4 && xch == 8 && slots * 16 * 64 * 4 + 4160 * (size_t)std::max(1u, out.voice_channels) <= 40 * 1024) out.wide4 = true;
+    for (size_t k = 0; k < cg.xvals.size(); ++k) {
+        const auto& xv = cg.xvals[k];
+        int far = group_of(groups, xv.from);
+        for (int u : xv.users) far = std::max(far, group_of(groups, u));
+        const int depth = far - group_of(groups, xv.from) + 1;
+        body << "    constexpr uint32_t XD" << k << " = " << (depth > 1 ? "FD_T ? FD_T : " : "") << depth << ";\n";
+        if (depth > 1) body << "    __shared__ float chan" << k << "[XD" << k << "][XCH][OG_WAVE];\n";
+    }
+    body << "    __shared__ uint32_t prog[" << K << "]; // flag hand-off: chunks completed, per stage\n"
+         << "    __shared__ uint32_t cons[" << K << "]; // ... and chunks whose inputs this stage has taken out of the rings\n"
+         << "    if constexpr (FD_T != 0) {\n"
+         << "        if (threadIdx.x < " << K << "u) prog[threadIdx.x] = cons[threadIdx.x] = 0u;\n"
+         << "        __syncthreads();\n"
+         << "    }\n";
+}
+
+// ---- pipelined kernels: workgroup = K waves over the same 64 voices ----------------------------
+// All waves take the same n_chunks + K - 1 steps, one barrier per step; at step t the wave of group
+// s works on hand-off chunk t - s.  A value produced by group a and read by group b lives in an LDS
+// ring of b - a + 1 chunks.  Which wave of the workgroup takes which group rotates with the
+// workgroup index, so that the SIMDs of a CU do not each collect one kind of stage.
+void BodyWriter::write_pipeline_kernel(const std::vector<std::vector<int>>& groups, int tag)
+{
+    const int K = (int)groups.size();
+    body << "\n// " << K << "-wave pipeline over the same 64 voices (small banks: more waves per SIMD).\n";
+    for (int gi = 0; gi < K; ++gi) {
+        body << "//   wave " << gi << ":";
+        for (int ni : order)
+            if (group_of(groups, cg.stage_of[ni]) == gi) body << " " << g.nodes[ni].name;
+        body << (gi == K - 1 ? " + the mix bus\n" : "\n");
+    }
+    // FD_T = 0: one workgroup barrier per hand-off (every wave one chunk behind its predecessor); FD_T >= 2: flag
+    // hand-off (og_kernel_rt.hip.h, handoff_wait / handoff_publish) over rings of FD_T chunks per crossing value
+    body << "template <bool RAMPS, bool TAPS, uint32_t XCH_T = 0, uint32_t FD_T = 0>\n"
+         << "__device__ __forceinline__ void voice_block_p" << tag << "(const OgBlockArgs& A)\n{\n"
+         << "    __shared__ og::" << (out.voice_channels > 1 ? "BusLdsN<" + std::to_string(out.voice_channels) + ">" : std::string("BusLds")) << " bus;\n";
+    pipeline_lds(groups);
+    const char* rot_expr[5] = {"0u", "blockIdx.x", "(blockIdx.x >> 3)", "(blockIdx.x >> 5)", "(blockIdx.x >> 8)"};
+    int rot = 1;
+    if (const char* er = ogabi::experiment_knob("OGC_ROT")) rot = std::max(0, std::min(4, atoi(er)));
+    body << "    const uint32_t stage = (threadIdx.x / OG_WAVE + " << rot_expr[rot] << ") % " << K << "u;\n"
+         << "    og::VoiceCtx c;\n"
+         << "    og::voice_begin_split<TAPS>(A, c);\n"
+         << cg.common_decl.str() << "    if (c.valid) {\n" << cg.common_load.str() << "    }\n"
+         << "    const uint32_t n_chunks = (A.frames + XCH - 1) / XCH;\n";
+    for (int gi = 0; gi < K; ++gi) {
+        PipelineWave w(*this, groups, gi);
+        w.prologue();
+        w.handoff_setup();
+        w.chunk_loop();
+        w.epilogue();
+    }
+    body << "    }\n}\n";
+}
+
+// a wave's branch of the kernel up to its chunk loop: priority, state, hand-off registers, tick and event lambdas
+void PipelineWave::prologue()
+{
+    int base_prio = 0;
+    body << (gi == 0 ? "    if (stage == 0) {\n" : "    } else if (stage == " + std::to_string(gi) + ") {\n");
+    {
+        // VALU issue on a SIMD is arbitrated by priority, then age (MI355X_MICROARCH.md).  The first wave of
+        // the pipeline (the light producer: envelopes, first operator) runs at priority 1: it never becomes
+        // the straggler its consumers wait for at the hand-off barrier.  Measured, fm_voice: two waves at
+        // 65 536 voices 0.0741 -> 0.0660 ms; four waves at 32 768 voices 0.0500 -> 0.0484 ms; raising the
+        // other waves as well (2,1 / 3,2,1,0) is no better.  OGC_PRIO="p0,p1[,p2,p3]" overrides.
+        // Round 4, four waves (depth-first order): the LAST wave (filter, bus) lowest, the first highest, the middle
+        // ones between -- 2,1,1,0.  Interleaved A/B at the driver's command, 65 536 voices: 1,0,0,0 3.08e11; 0,0,0,0
+        // 3.00e11; 0,0,1,0 3.20e11; 1,1,1,0 3.16e11; 2,1,1,0 3.26e11; 3,2,1,0 3.27e11; 3,2,2,0 3.28e11; 2,1,2,0 3.28e11;
+        // 3,2,1,1 3.14e11 -- whatever is upstream must not wait for the wave that closes the chunk; the exact levels
+        // above it are within noise.  (Neutral on the 188-block run, +1 % at 32 768 and 131 072 voices.)
+        std::vector<int> pr = K >= 3 ? std::vector<int>{2, 1, 1, 0} : std::vector<int>{1, 0, 0, 0};
+        if (K >= 3) {
+            pr.assign((size_t)K, 1);
+            pr.front() = 2;
+            pr.back() = 0;
+        }
+        if (const char* ep = ogabi::experiment_knob("OGC_PRIO")) {
+            pr.clear();
+            for (const char* q = ep; *q; ++q)
+                if (isdigit((unsigned char)*q)) pr.push_back(*q - '0');
+        }
+        base_prio = gi < (int)pr.size() ? pr[gi] : 0;
+        // Round 6, flag hand-off (FD_T != 0): the order turns round -- 0,1,2,3, downstream first.  Without the barrier a
+        // consumer that has its inputs runs them down at once and the producers fill in behind it; the rings stay near
+        // empty and no wave sits blocked on a full one.  Interleaved A/B, 65 536 voices, 16-frame chunks, rings of 2
+        // (profiles/r06_handoff_ab.md): barrier 2,1,1,0 (round 5) 5.45e11 at the driver's command; flags 2,1,1,0
+        // 5.56e11; flags 0,0,0,0 5.40e11; flags 0,1,1,2 5.65e11; 0,0,1,2 5.74e11; 0,1,2,2 5.57e11; 1,1,2,3 5.38e11;
+        // 0,0,2,3 5.32e11; flags 0,1,2,3 5.93e11 -- and the barrier with 0,1,2,3 4.89e11: the order only works without
+        // the lock step.  Moving-cutoff variant 3.95e11 -> 4.37e11; 188-block regions 6.42e11 -> 6.2e11 (-3 %).
+        const int flag_prio = ogabi::experiment_knob("OGC_PRIO") ? base_prio : std::min(gi, 3);
+        body << "    constexpr int BASE_PRIO = FD_T != 0 ? " << flag_prio << " : " << base_prio << ";\n"
+             << "    og::set_prio<BASE_PRIO>();\n";
+    }
+    body << bw.cat(st, &Codegen::Sect::decl) << "    if (c.valid) {\n" << bw.cat(st, &Codegen::Sect::load) << "    }\n";
+    body << "    auto derive = [&]() __attribute__((always_inline)) {\n" << bw.cat(st, &Codegen::Sect::derive) << "    };\n";
+    body << bw.cat(st, &Codegen::Sect::pre) << "    derive();\n";
+    // hand-off values this wave reads: fetched for the whole chunk before its first tick, so that the LDS
+    // latency is paid once per chunk and not in front of every frame's first dependent instruction
+    for (size_t k = 0; k < cg.xvals.size(); ++k) {
+        const auto& xv = cg.xvals[k];
+        bool used_here = false;
+        for (int u : xv.users) used_here = used_here || bw.group_of(groups, u) == gi;
+        if (used_here && bw.group_of(groups, xv.from) != gi) reads.push_back(k);
+    }
+    for (size_t k : reads) body << "    float xp" << k << "[XCH];\n";
+    // Release reciprocals from a table (four-wave shapes; the sticky release loop below, wide form only, og::rcp_fetch):
+    // one 16-byte load per envelope and four frames instead of v_rcp_f32 + a subtraction per envelope and frame.
+    // OGC_RCP_TAB=0 keeps v_rcp_f32 in that loop (A/B).
+    if (K == 4 && !(ogabi::experiment_knob("OGC_RCP_TAB") && atoi(ogabi::experiment_knob("OGC_RCP_TAB")) == 0))
+        for (int k : st)
+            for (const auto& cexp : cg.sec[k].env_cnts) envs.push_back(cexp.substr(0, cexp.size() - 4)); // "<E>.cnt"
+    for (const auto& E : envs) body << "    float " << E << "_rcp[XCH];\n";
+    // Ramp-table rows (ramped inputs: the RAMPS variants; stream inputs: every variant).  `RV(row, slot)` / `ST(row)`
+    // read A.ramp_table[row * stride + f] -- a scalar load behind a 64-bit address computation, per input and frame:
+    // the launches that read the table took 1.8x the time of the others (SALU 2.9x per block, round 5 counters).  In
+    // the unrolled chunk bodies the rows this wave reads are fetched for the WHOLE chunk at its top, next to the
+    // hand-off values (consecutive words from a uniform base: wide scalar loads); the rolled event path keeps the
+    // direct read.  RV -> RVP / ST -> STP in this wave's tick text.
+    tick_text = bw.group_tick(groups, gi);
+    for (const char* mac : {"RV(", "ST("}) {
+        const std::string pre_mac = std::string(mac, 2) + "P(";
+        for (size_t pos = tick_text.find(mac); pos != std::string::npos; pos = tick_text.find(mac, pos + 1)) {
+            if (pos > 0 && (isalnum((unsigned char)tick_text[pos - 1]) || tick_text[pos - 1] == '_')) continue;
+            rows.insert(atoi(tick_text.c_str() + pos + 3));
+            tick_text.replace(pos, 3, pre_mac);
+        }
+    }
+    for (int r : rows) body << "    float rv_" << r << "[XCH];\n";
+    for (const auto& E : envs) {
+        const std::string from = "og::adsr_tick<decltype(chk)::release, true>(" + E + ")";
+        const std::string to = "og::adsr_tick_chunk<decltype(chk)::release, decltype(chk)::table>(" + E + ", " + E + "_rcp, j)";
+        const size_t pos = tick_text.find(from);
+        if (pos == std::string::npos) throw std::runtime_error("internal: no tick of " + E + " in its wave");
+        tick_text.replace(pos, from.size(), to);
+    }
+    body << "    auto tick = [&](const uint32_t f, const uint32_t ch, const uint32_t j, auto chk) __attribute__((always_inline))"
+         << (last ? (out.voice_channels > 1 ? " -> og::OutN<" + std::to_string(out.voice_channels) + ">" : std::string(" -> float")) : std::string()) << " {\n"
+         << tick_text;
+    if (last) body << "        return " << bw.bus_expr << ";\n";
+    body << "    };\n";
+    body << bw.events_code(st);
+}
+
+// SALU instructions cost issue slots like VALU ones: the quiet chunk is a straight-line,
+// fully unrolled body; per-frame tests only exist on the (rare) event path
+std::string PipelineWave::call(const std::string& flag) const
+{
+    const std::string t = std::string("tick(f, ch, j, og::BoolC<") + flag + ">{})";
+    // row of the bus tile: f % OG_BUS_CHUNK = (base % OG_BUS_CHUNK) + j -- `base` is a multiple of XCH, which divides
+    // OG_BUS_CHUNK, so there is no carry; written this way the chunk-invariant part is formed once per chunk and the
+    // eight stores of the unrolled body take immediate offsets (one v_add + two SALU per frame less in the bus wave)
+    return last ? "og::bus_put<TAPS>(A, c, bus, f, (base & (OG_BUS_CHUNK - 1u)) + j, " + t + ");" : t + ";";
+}
+
+void PipelineWave::handoff_setup()
+{
+    // node steady-state conditions of this wave's stages (Sect::fast_conds), as in the ordinary kernel
+    for (int k : st)
+        for (const auto& fc : cg.sec[k].fast_conds) steady += (steady.empty() ? "" : " && ") + fc;
+    // flags: stage-end checks, release arithmetic, hand-off values prefetched, node steady states
+    // `stay` (sticky chunks): the condition -- on the NEXT chunk, `base1` -- under which this very variant runs again.
+    // The wave then stays in a loop of its own around the variant's body (hand-off barrier inside) instead of
+    // going back through the chunk loop's head.  Why: the chunk loop merges four bodies (two quiet variants, the
+    // checked one, the rolled one) and the compiler brings every loop-carried value (envelope, phases, event
+    // cursor: ~20 registers) back to one place after each of them -- 30 v_mov + ~40 SALU per wave and chunk, a sixth
+    // of a quiet chunk's instructions (scripts/isa_blocks.py).  A loop with ONE body keeps its values where they are.
+    // Static count, fm_voice four-wave kernel, release-free quiet chunk of waves 0-2: 231 + 230 + 222 -> ~201 + 187 + 194
+    // VALU per 8 frames; rocprofv3 SQ_INSTS_VALU per 64-voice frame at the driver's command 120.7 -> 107.4.  Interleaved A/B on one MI355X, 65 536 voices: 94-block
+    // runs 3.73e11 -> 4.01e11, the driver's command 3.29e11 -> 3.54e11, 131 072 voices 3.90e11 -> 4.20e11 (+7.5 % each);
+    // parity subset of the GPU suite green with the variant before it became the default.  OGC_STICKY=0 turns it off.
+    sticky = !(ogabi::experiment_knob("OGC_STICKY") && atoi(ogabi::experiment_knob("OGC_STICKY")) == 0) && !ogabi::experiment_knob("OGC_FORCE_PATH");
+    // hand-off partners of this wave: the stages whose values it reads (producers) and the stages that read its values
+    for (const auto& xv : cg.xvals) {
+        const int from = bw.group_of(groups, xv.from);
+        for (int u : xv.users) {
+            const int to = bw.group_of(groups, u);
+            if (to == from) continue;
+            if (to == gi) producers.insert(from);
+            if (from == gi) consumers.insert(to);
+        }
+    }
+    for (int q : producers) body << "    uint32_t seen_p" << q << " = 0u;\n";
+    for (int q : consumers) body << "    uint32_t seen_c" << q << " = 0u;\n";
+    // flags: before chunk `ch` -- its inputs are complete, and the ring slots it writes have been read
+    wait_all = "if constexpr (FD_T != 0) {";
+    for (int q : producers) wait_all += " og::handoff_wait(&prog[" + std::to_string(q) + "], seen_p" + std::to_string(q) + ", ch + 1u);";
+    for (int q : consumers) wait_all += " og::handoff_wait(&cons[" + std::to_string(q) + "], seen_c" + std::to_string(q) + ", ch + 1u - FD_T);";
+    wait_all += " }";
+    // (a stage that reads hand-off values gives their ring slots back as soon as the chunk's values sit in its registers --
+    //  `taken`, after the prefetch of the unrolled bodies -- or, on the rolled path, with the chunk)
+    taken = producers.empty() ? std::string()
+                                                : "if constexpr (FD_T != 0) og::handoff_publish(&cons[" + std::to_string(gi) + "], ch + 1u);";
+    sync_line = "if constexpr (FD_T != 0) { og::handoff_publish(&prog[" + std::to_string(gi) + "], ch + 1u);" +
+                                  (producers.empty() ? std::string() : " __hip_atomic_store(&cons[" + std::to_string(gi) + "], ch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);") +
+                                  " } else OG_HANDOFF_BARRIER(); // hand-off: chunk `ch` of this stage is complete";
+}
+
+std::string PipelineWave::bus_tail(const std::string& ind, const std::string& n_expr) const
+{
+    static const std::string bus_tail_fmt = // %B = first frame of the finished chunk, %N = its length
+        "{ // the bus tile holds OG_BUS_CHUNK frames = OG_BUS_CHUNK / XCH hand-offs\n"
+        "%I    const uint32_t lastf = %B + %N - 1;\n"
+        "%I    if ((lastf % OG_BUS_CHUNK) == OG_BUS_CHUNK - 1 || lastf + 1 == A.frames)\n"
+        "%I        og::bus_chunk_reduce(A, c, bus, lastf - (lastf % OG_BUS_CHUNK), (lastf % OG_BUS_CHUNK) + 1);\n"
+        "%I}\n";
+    std::string o = ind + bus_tail_fmt;
+    auto sub = [&](const std::string& k, const std::string& v) {
+        for (size_t q = o.find(k); q != std::string::npos; q = o.find(k, q + v.size())) o.replace(q, k.size(), v);
+    };
+    sub("%I", ind);
+    sub("%B", "base");
+    sub("%N", n_expr);
+    return o;
+}
+
+// the table rows of this chunk (`base` = its first frame within the launch)
+std::string PipelineWave::row_fetch(const std::string& ind) const
+{
+    std::ostringstream o;
+    if (rows.empty()) return std::string();
+    bool only_ramps = true; // (ST rows -- stream inputs -- are read in every variant, RV rows only under RAMPS)
+    for (size_t pos = tick_text.find("STP("); pos != std::string::npos; pos = std::string::npos) only_ramps = false;
+    o << ind << (only_ramps ? "if (RAMPS) {\n" : "{\n");
+    for (int r : rows)
+        o << ind << "    og::row_fetch<XCH>(rv_" << r << ", A.ramp_table + (size_t)" << r << " * A.ramp_stride + base);\n";
+    o << ind << "}\n";
+    return o.str();
+}
+
+// The quiet release loop of the four-wave form takes its reciprocals from the table in the wide instantiation
+// (FD_T != 0; the 8-frame one keeps v_rcp_f32): one 16-byte load per envelope and four frames.  A wide launch whose
+// releases the table does not cover (rcp_len = 0) sends chunks with a releasing lane to the checked body instead
+// (`rel_ok` in the quiet test below).  Only where the checked body is the alternative (one_checked).
+void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay)
+{
+    const bool pre = !reads.empty() || !rows.empty();
+    const bool loop = sticky && !stay.empty();
+    const std::string ind = loop ? ind0 + "    " : ind0;
+    const bool tab = tab_ok && loop && !envs.empty() && std::string(chk_flag) == "false" && std::string(rel_flag) == "true";
+    if (tab) {
+        body << ind0 << "if constexpr (FD_T != 0) { // the first chunk's release reciprocals\n";
+        for (const auto& E : envs) body << ind0 << "    og::rcp_fetch<XCH>(" << E << "_rcp, A, " << E << ".cnt);\n";
+        body << ind0 << "}\n";
+    }
+    if (loop) body << ind0 << "for (;;) { // sticky: this variant again while its conditions hold\n";
+    if (tab)
+        for (const auto& E : envs) body << ind << "const uint32_t " << E << "_nx = " << E << ".cnt - XCH; // (at the next chunk's top)\n";
+    if (std::string(rel_flag) == "true") {
+        if (tab) body << ind << "if constexpr (FD_T == 0) {\n" << bw.fc_sync(st, ind + "    ") << ind << "}\n";
+        else body << bw.fc_sync(st, ind);
+    }
+    if (pre) {
+        body << row_fetch(ind);
+        body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
+        for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
+        body << ind << "}\n";
+        if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
+    }
+    const std::string flag = std::string(chk_flag) + ", " + rel_flag + ", " + (pre ? "true" : "false") + ", " +
+                             (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "");
+    body << ind << "#pragma unroll\n"
+         << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
+         << ind << "    const uint32_t f = base + j;\n"
+         << ind << "    " << call(flag) << "\n";
+    // (the next chunk's four reciprocals go into the registers these frames have just read: nothing moves across the
+    //  back edge; a chunk the loop then leaves has loaded them for nothing, inside the table's padding)
+    if (tab) {
+        body << ind << "    if constexpr (FD_T != 0) {\n";
+        for (const auto& E : envs) body << ind << "        og::rcp_refill<XCH>(" << E << "_rcp, A, " << E << "_nx, j);\n";
+        body << ind << "    }\n";
+    }
+    body << ind << "}\n";
+    if (loop) {
+        body << ind << "const uint32_t ch1 = ch + 1u, base1 = base + XCH;\n"
+             << ind << "if (!(ch1 < n_chunks && A.frames - base1 >= (uint32_t)XCH && " << stay_path << (stay == "1" ? "" : " && " + stay)
+             << ")) break;\n";
+        if (last) body << bus_tail(ind, "XCH");
+        body << ind << sync_line << "\n"
+             << ind << "++t;\n" << ind << "ch = ch1;\n" << ind << "base = base1;\n";
+        if (!wait_all.empty()) body << ind << wait_all << "\n";
+        body << ind0 << "}\n";
+    }
+}
+
+// the checked chunk: unrolled, stage-end checks and release arithmetic on, events applied on their frame
+void PipelineWave::checked(const std::string& ind)
+{
+    const bool pre = !reads.empty() || !rows.empty();
+    body << bw.fc_sync(st, ind);
+    if (pre) {
+        body << row_fetch(ind);
+        body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
+        for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
+        body << ind << "}\n";
+        if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
+    }
+    const std::string flag = std::string("true, true, ") + (pre ? "true" : "false") + ", false";
+    body << ind << "#pragma unroll\n"
+         << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
+         << ind << "    const uint32_t f = base + j;\n"
+         << ind << "    if (__any((int)(f == c.next_ev))) events(f); // (wave-uniform: rare)\n"
+         << ind << "    " << call(flag) << "\n"
+         << ind << "}\n";
+}
+
+void PipelineWave::variants(bool st_flag, const std::string& ind0)
+{
+    if (force && force[0] == 'c') {
+        quiet("true", "true", st_flag, ind0);
+    } else if (mc.empty()) {
+        quiet("true", "true", st_flag, ind0, "1");
+    } else {
+        const std::string no_end = "__all((int)(" + mc + " > (uint32_t)XCH))", no_rel = "__all((int)(" + bw.rs_sum(st) + " == 0.0f))";
+        body << ind0 << "if (" << no_end << ") { // no envelope stage ends in this chunk\n"
+             << ind0 << "    if (" << no_rel << ") { // ... and no lane is in Release\n";
+        quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "        ", no_end + " && " + no_rel);
+        body << ind0 << "    } else {\n";
+        quiet("false", "true", st_flag, ind0 + "        ", no_end + " && !" + no_rel);
+        body << ind0 << "    }\n" << ind0 << "} else {\n";
+        quiet("true", "true", st_flag, ind0 + "    ");
+        body << ind0 << "}\n";
+    }
+}
+
+// the two straight-line variants only (the caller has established that no countdown ends in the chunk)
+void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
+{
+    const std::string no_rel = "__all((int)(" + bw.rs_sum(st) + " == 0.0f))";
+    body << ind0 << "if (" << no_rel << ") { // no lane is in Release\n";
+    quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "    ", no_rel);
+    body << ind0 << "} else {\n";
+    // OGC_RELPRIO=n (experiment for grouped banks, og_group_voices: the waves that release are then few and
+    // whole, and their workgroups are the ones a launch waits for; measured WITHOUT grouping in round 4: loses)
+    if (rel_prio >= 0) body << ind0 << "    __builtin_amdgcn_s_setprio(" << rel_prio << ");\n";
+    quiet("false", "true", st_flag, ind0 + "    ", "!" + no_rel);
+    if (rel_prio >= 0) body << ind0 << "    og::set_prio<BASE_PRIO>();\n";
+    body << ind0 << "}\n";
+}
+
+void PipelineWave::chunk_loop()
+{
+    mc = bw.min_cnt(st);
+    // ---- events in the pipelined kernels -----------------------------------------------------------------
+    // (1) A wave only has to leave the straight-line path for events IT handles.  Every wave of the pipeline
+    //     walks the voice's event list, but e.g. FMVoice's second wave (operators 2 and 1, filter) has no
+    //     handler for `gate` -- only the envelope wave has -- and used to run the chunk frame by frame for
+    //     nothing.  Events without a handler in this wave's stages are consumed at the top of the chunk.
+    // (2) A chunk that does hold an event (or an envelope stage end) runs the UNROLLED body with one
+    //     wave-uniform `any lane has an event on this frame` test per frame, instead of a rolled frame loop
+    //     that serialises the frames (measured: the rolled event chunk costs twice a quiet one, and the launch
+    //     ends with the wave that met the most events).  It replaces the stage-end-check variant of the quiet
+    //     chunk, so the kernel does not grow.
+    // Measured (scripts/dbg_event_cost.py, fm_voice, 65 536 voices, kernel ms per 256-frame block, round-2 form ->
+    // both): one retrigger per voice in 5 120 frames 0.0641 -> 0.0623, two 0.0714 -> 0.0677 (the cost of an
+    // event falls by a third, nearly all of it from (1)) -- but (2) inlines the handlers into every frame of the
+    // checked body (two-wave kernel 26.8 -> 35.9 KB) and the QUIET path pays for it: idle bank 0.0514 -> 0.0528,
+    // sustaining 0.0536 -> 0.0553.  At the benchmark's event density the two cancel (2.73e11 either way), so
+    // (1) was on and (2) off through round 3: OGC_EVSKIP=0 turns (1) off.
+    const bool ev_skip = !(ogabi::experiment_knob("OGC_EVSKIP") && atoi(ogabi::experiment_knob("OGC_EVSKIP")) == 0);
+    // (round 4: (2) is ON -- with the event records prefetched into registers (og::VoiceCtx::nx_*) the handlers inlined
+    //  into the checked body no longer carry loads and waits; four-wave kernel at 65 536 voices, interleaved A/B:
+    //  3.07e11 either way at the driver's command, 3.57e11 against 3.44e11 on the 188-block run; OGC_EVUNROLL=0 turns it off)
+    const bool ev_unroll = !(ogabi::experiment_knob("OGC_EVUNROLL") && atoi(ogabi::experiment_knob("OGC_EVUNROLL")) == 0);
+    std::string relevant; // condition on `tgt`: this wave has a handler for the event
+    {
+        const std::string code = bw.cat(st, &Codegen::Sect::derive) + bw.group_tick(groups, gi) + bw.cat(st, &Codegen::Sect::decl);
+        for (size_t i = 0; i < out.inputs.size(); ++i) {
+            const InputInfo& in = out.inputs[i];
+            if (!(in.decl.kind == Kind::Value && in.decl.per_voice)) continue;
+            const std::string var = "vin_" + std::to_string(i);
+            bool used = false;
+            for (size_t p = code.find(var); p != std::string::npos && !used; p = code.find(var, p + 1)) {
+                const size_t e = p + var.size();
+                used = e >= code.size() || !isdigit((unsigned char)code[e]);
+            }
+            // (the first wave stores the per-voice inputs back: it applies every SETVALUE)
+            if (used || gi == 0) relevant += (relevant.empty() ? "" : " || ") + ("tgt == (OG_EV_SETVALUE | " + std::to_string(i) + "u)");
+        }
+        std::set<int> handled;
+        for (int k : st)
+            for (auto& kv : cg.sec[k].ev_handlers)
+                if (!kv.second.str().empty()) handled.insert(kv.first);
+        for (int h : handled) relevant += (relevant.empty() ? "" : " || ") + ("tgt == " + std::to_string(h) + "u");
+        if (relevant.empty()) relevant = "false";
+    }
+    force = ogabi::experiment_knob("OGC_FORCE_PATH"); // experiment knob: b | c | ev -- quiet chunks take the release-arithmetic / stage-end-check / event path (results stay valid)
+    rel_prio = ogabi::experiment_knob("OGC_RELPRIO") ? atoi(ogabi::experiment_knob("OGC_RELPRIO")) : -1;
+    if (last) body << "    og::bus_init(c, bus); // (this wave owns the tile)\n";
+    body << "    for (uint32_t t = 0; t < n_chunks + (FD_T ? 0u : " << (K - 1) << "u); ++t) {\n"
+         << "        " << (sticky ? "" : "const ") << "uint32_t ch = t - (FD_T ? 0u : " << gi << "u);\n"
+         << "        if (ch < n_chunks) {\n";
+    if (!wait_all.empty()) body << "        " << wait_all << "\n";
+    body
+         << "        " << (sticky ? "" : "const ") << "uint32_t base = ch * XCH;\n"
+         << "        const uint32_t n = min((uint32_t)XCH, A.frames - base);\n";
+    if (ev_skip && relevant != "true")
+        body << "        if (!__all((int)(c.next_ev >= base + XCH))) { // consume the events this wave has no handler for\n"
+             << "            while (c.next_ev < base + XCH) {\n"
+             << "                const uint32_t tgt = c.nx_target;\n"
+             << "                if (" << relevant << ") break;\n"
+             << "                og::ev_advance(A, c);\n"
+             << "            }\n"
+             << "        }\n";
+    // A wave that meets an event or an envelope stage end runs the checked body for that chunk -- about twice the
+    // work of a quiet one -- and the other waves of its workgroup wait for it at the hand-off barrier: it runs
+    // that chunk at the highest priority and drops back afterwards.  Interleaved A/B, fm_voice, 65 536 voices,
+    // 94-block runs, nine pairs: +0.9 .. +5.8 %, mean +2.1 % (3.68e11 -> 3.76e11); level 2 instead of 3 gives a
+    // third of it; neutral at 32 768 and 262 144 voices; raising the release-arithmetic variant as well loses
+    // the gain.  (The two-wave kernel carries it too although it does nothing for it -- forced with
+    // OSCEN_GPU_SPLIT=2 at 65 536 voices: 3.16e11 with, 3.19e11 without; the engine does not pick that kernel at
+    // any bank size of the bench.)  OGC_SLOWPRIO=-1 turns it off.
+    const int slow_prio = ogabi::experiment_knob("OGC_SLOWPRIO") ? atoi(ogabi::experiment_knob("OGC_SLOWPRIO")) : 3;
+    const bool one_checked = ev_unroll && !mc.empty() && !force; // events and stage ends share ONE unrolled, checked body
+    tab_ok = one_checked && !envs.empty();
+    const std::string rel_ok = tab_ok ? " && (FD_T == 0 || A.rcp_len != 0u || __all((int)(" + bw.rs_sum(st) + " == 0.0f)))" : std::string();
+    if (one_checked)
+        body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH)) && __all((int)(" << mc
+             << " > (uint32_t)XCH))" << rel_ok << ") { // nothing happens in this chunk: no event, no envelope stage end\n";
+    else
+        body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH))" << (force && force[0] == 'e' ? " && A.frames == 0u" : "") << ") {\n";
+    auto pick = [&](bool st_flag, const std::string& ind) {
+        if (one_checked) fast_variants(st_flag, ind);
+        else variants(st_flag, ind);
+    };
+    const std::string stay_entry = std::string("__all((int)(c.next_ev >= base1 + XCH))") +
+                                   (one_checked ? " && __all((int)(" + mc + " > (uint32_t)XCH))" : std::string());
+    if (steady.empty()) {
+        stay_path = stay_entry;
+        pick(false, "            ");
+    } else {
+        const std::string all_steady = "__all((int)(!c.valid || (" + steady + ")))";
+        body << "            constexpr uint32_t CHUNK = XCH;\n"
+             << "            if (" << all_steady << ") { // node steady states hold for the whole chunk\n";
+        stay_path = stay_entry + " && " + all_steady;
+        pick(true, "                ");
+        body << "            } else {\n";
+        stay_path = stay_entry + " && !" + all_steady;
+        pick(false, "                ");
+        body << "            }\n";
+    }
+    if (one_checked && ogabi::experiment_knob("OGC_STAGEEND_BODY") && atoi(ogabi::experiment_knob("OGC_STAGEEND_BODY")) != 0) {
+        // experiment (round 6): a chunk with a stage end but NO event takes a body with the stage-end checks and without
+        // the per-frame event tests and the inlined handlers
+        body << "        } else if (n == XCH && __all((int)(c.next_ev >= base + XCH))) { // a stage end, no event\n";
+        if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << ");\n";
+        quiet("true", "true", false, "            ");
+        if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
+    }
+    if (one_checked) {
+        body << "        } else if (n == XCH) { // an event or a stage end in this chunk: the checked, unrolled body\n";
+        if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << "); // the wave on the slow path is the straggler\n";
+        checked("            ");
+        if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
+    }
+    body << "        } else {\n"
+         << bw.fc_sync(st, "            ")
+         << "            for (uint32_t j = 0; j < n; ++j) {\n"
+         << "                const uint32_t f = base + j;\n"
+         << "                events(f);\n"
+         << "                " << call("true") << "\n"
+         << "            }\n"
+         << "        }\n";
+    if (last) body << bus_tail("        ", "n");
+    body << "        }\n"
+         << "        " << sync_line << "\n"
+         << "    }\n";
+}
+
+void PipelineWave::epilogue()
+{
+    if (last) body << "    og::bus_flush(A, c, bus);\n";
+    body << bw.cat(st, &Codegen::Sect::pre_store) << "    if (c.valid) {\n" << bw.cat(st, &Codegen::Sect::store)
+         << (gi == 0 ? bw.vin_store() : std::string()) << "    }\n";
+    if (gi == 0) body << "    og::voice_end(A, c);\n";
+}
+
+// ---- the driver ------------------------------------------------------------------------------------------
+// One pass over a graph: everything lower() makes.  Codegen holds string streams, so a pass lives where it was built.
+struct Lowered {
+    const GraphDesc g; // the description with arrays, nested graphs and poly wrappers expanded
+    std::unique_ptr<CompiledGraph> out;
+    Codegen cg;
+    Lowering lw;
+    std::string body; // the kernels' text: what goes into the unit's namespace
+    explicit Lowered(const GraphDesc& g_in) : g(expand(g_in)), out(std::make_unique<CompiledGraph>()), cg(g, *out), lw(cg) {}
+};
+
+// The phases of a pass, in order.  zero_nodes == null: the general kernel; otherwise the nodes a zero variant folds.
+//   check_reference_rules     the description as written                        -> the reference's refusals
+//   declare_inputs_outputs    g.inputs, g.outputs                               -> out.inputs, slots / state / table rows, name maps
+//   declare_nodes             g.nodes                                           -> cg.nodes, cg.N, the post-mix stage of `out`
+//   infer_overwritten_edges   g.edges, declared kinds                           -> the edges a later edge into a value input replaces
+//   wire_edges                g.edges, that set                                 -> in_edges / ev_edges of the nodes, deps, out_edges, bus ends
+//   prune_dead_nodes          deps, out_deps                                    -> NodeInst::live, out.lpv / lane_width, cg.dynamic_events
+//   kahn_order                deps of the live nodes                            -> order (the reference's)
+//   schedule_order            order, deps, node weights                         -> order (depth first from the sinks), out.node_order
+//   assign_rate_domains       order, deps                                       -> NodeInst::domain
+//   plan_pipeline_stages      order, in_edges, out_edges                        -> cg.stage_of, n_stages, groups2, groups4
+//   find_inner_event_sources  order, ev_node_edges, ev_out_edges                -> cg.ev_capacity, inner / outer_ev_sources
+//   emit_nodes                order, domains, stages                            -> cg.sec[], slots and state of the nodes, out.schedule_order
+//   form_graph_output         out_edges, out_reads, ev_out_edges, the bus ends  -> bus_expr, out.output_channels / event_outputs / channels
+//   choose_unroll             order, out.rings / players / lpv                  -> unroll, out.valu_estimate
+//   BodyWriter                cg.sec[], cg.xvals, the groups, bus_expr, unroll  -> body
+std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_nodes)
+{
+    check_reference_rules(g_in);
+    auto gen = std::make_unique<Lowered>(g_in);
+    gen->out->name = gen->g.name;
+    Codegen& cg = gen->cg;
+    cg.zero_nodes = zero_nodes;
+    Lowering& lw = gen->lw;
+    lw.declare_inputs_outputs();
+    lw.declare_nodes();
+    lw.wire_edges(lw.infer_overwritten_edges());
+    lw.prune_dead_nodes();
+    lw.kahn_order();
+    lw.schedule_order();
+    lw.assign_rate_domains();
+    lw.plan_pipeline_stages();
+    lw.find_inner_event_sources();
+    lw.emit_nodes();
+    lw.form_graph_output();
+    lw.choose_unroll();
+    BodyWriter bw(lw);
+    bw.write_ordinary_kernel();
+    if (!cg.groups2.empty()) bw.write_pipeline_kernel(cg.groups2, 2);
+    if (!cg.groups4.empty()) bw.write_pipeline_kernel(cg.groups4, 4);
+    for (const auto& kv : cg.user_fns) gen->body += kv.second;
+    gen->body += bw.body.str();
+    return gen;
+}
+
+// A zero variant's pass: the kernel body with `nodes` folded, or "" where the graph does not get that variant.  The engine
+// fills the slots and the state of every kernel from the general pass's layout: a variant pass that does not keep it (or does
+// not compile) leaves the graph without the variant -- it never costs the graph its general kernel.
+std::string lower_variant(const GraphDesc& g_in, const std::set<int>& nodes, const CompiledGraph& out)
+{
+    if (nodes.empty()) return std::string();
+    try {
+        const auto zgen = lower(g_in, &nodes);
+        const CompiledGraph& z = *zgen->out;
+        bool same = z.n_slots == out.n_slots && z.state.size() == out.state.size() && z.n_ramps == out.n_ramps && z.n_streams == out.n_streams &&
+                    z.lpv == out.lpv && z.max_pipeline == out.max_pipeline && z.wide4 == out.wide4;
+        for (size_t i = 0; same && i < out.state.size(); ++i) same = z.state[i].name == out.state[i].name;
+        return same ? zgen->body : std::string();
+    } catch (const std::exception&) {
+        return std::string();
+    }
+}
+
+struct ZeroFolds {
+    std::set<int> nodes, zeros, guards; // the folded nodes; the slots that must hold +-0 / be finite for the launch
+};
+
+// ZeroChains (above): the Gain / AddValue nodes and the slots the engine tests
+std::set<int> find_zero_chain(Lowered& gen)
+{
+    Codegen& cg = gen.cg;
+    const GraphDesc& g = gen.g;
+    CompiledGraph& out = *gen.out;
     std::set<int> zset;
     const char* zk = ogabi::experiment_knob("OGC_ZERO_SPEC");
     for (const NodeInst& d : cg.nodes) {
@@ -5021,175 +5289,181 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         zset.insert(d.id);
         out.zero_slots.push_back(gs->second);
     }
-    std::string zbody;
-    if (!zset.empty()) {
-        // the engine fills the slots and the state of both kernels from this pass's layout: a zero pass that does not keep it
-        // (or does not compile) leaves the graph without the variant -- it never costs the graph its general kernel
-        bool same = false;
-        try {
-            const auto z = compile_pass(g_in, &zset, &zbody);
-            same = z->n_slots == out.n_slots && z->state.size() == out.state.size() && z->n_ramps == out.n_ramps &&
-                   z->n_streams == out.n_streams && z->lpv == out.lpv && z->max_pipeline == out.max_pipeline && z->wide4 == out.wide4;
-            for (size_t i = 0; same && i < out.state.size(); ++i) same = z->state[i].name == out.state[i].name;
-        } catch (const std::exception&) {
-            same = false;
-        }
-        if (!same) {
-            zset.clear();
-            zbody.clear();
-            out.zero_slots.clear();
-        }
-    }
-    // ZeroFolds (above): the FmOperator / Crossfade / Mixer nodes of the deeper zero variant, the slots the engine tests
+    return zset;
+}
+
+// ZeroFolds (above): the FmOperator / Crossfade / Mixer nodes of the deeper zero variant, the slots the engine tests
+ZeroFolds find_zero_folds(Lowered& gen)
+{
+    Codegen& cg = gen.cg;
+    const GraphDesc& g = gen.g;
+    const CompiledGraph& out = *gen.out;
     std::set<int> z2set;
-    std::string z2body;
-    {
-        const char* z2k = ogabi::experiment_knob("OGC_ZERO2_SPEC");
-        std::set<int> fb_ops, xfades, mixers; // candidates (node indices), thinned out until every one of them passes its rule
-        auto usable = [&](const NodeInst& n, Emitter type) { return n.live && n.type && n.type->emit == type && n.domain != 1; };
-        for (const NodeInst& d : cg.nodes) {
-            if (z2k && atoi(z2k) == 0) break;
-            auto slot_of = [&](const std::map<int, int>& m) {
-                auto it = m.find(d.id);
-                return it == m.end() ? -1 : it->second;
-            };
-            if (usable(d, emit_fm_operator) && slot_of(cg.fm_fb_slot) >= 0) fb_ops.insert(cg.node_by_name.at(d.decl->name));
-            if (usable(d, emit_crossfade) && slot_of(cg.xfade_mix_slot) >= 0) xfades.insert(cg.node_by_name.at(d.decl->name));
-            if (usable(d, emit_mixer)) mixers.insert(cg.node_by_name.at(d.decl->name));
-        }
-        // the one plain `node.port` source of an input: (node index, port); (-1, "") for anything else -- an unconnected input,
-        // an expression, a fan-in, a policy edge
-        auto src_ref = [&](const NodeInst& n, const std::string& port) -> std::pair<int, std::string> {
-            auto it = n.in_edges.find(port);
-            if (it == n.in_edges.end() || it->second.size() != 1) return {-1, ""};
-            const NodeInst::Src& sr = it->second[0];
-            if (!sr.policy.empty() || sr.e->t != Expr::Ref || sr.e->port.empty()) return {-1, ""};
-            auto ni = cg.node_by_name.find(sr.e->node);
-            if (ni == cg.node_by_name.end() || cg.nodes[ni->second].domain != n.domain) return {-1, ""};
-            return {ni->second, sr.e->port};
+    const char* z2k = ogabi::experiment_knob("OGC_ZERO2_SPEC");
+    std::set<int> fb_ops, xfades, mixers; // candidates (node indices), thinned out until every one of them passes its rule
+    auto usable = [&](const NodeInst& n, Emitter type) { return n.live && n.type && n.type->emit == type && n.domain != 1; };
+    for (const NodeInst& d : cg.nodes) {
+        if (z2k && atoi(z2k) == 0) break;
+        auto slot_of = [&](const std::map<int, int>& m) {
+            auto it = m.find(d.id);
+            return it == m.end() ? -1 : it->second;
         };
-        auto dropped_in = [&](const NodeInst& m, const char* port) { // a Mixer input that reads a folded Crossfade's output_b
-            const auto r = src_ref(m, port);
-            return r.first >= 0 && r.second == "output_b" && xfades.count(r.first) > 0;
-        };
-        // An operator whose output is finite on every frame, given finite levels: sin and an ADSR level are bounded, the level is
-        // a finite literal or a slot the engine tests (`guards`), and nothing non-finite can reach the sine -- the feedback term
-        // is absent or folded, the phase modulation comes from such operators through folded nodes only.
-        std::function<bool(int, int, std::set<int>*)> finite_op;
-        std::function<bool(int, const std::string&, int, std::set<int>*)> finite_src = [&](int ni, const std::string& port, int depth, std::set<int>* guards) {
-            const NodeInst& n = cg.nodes[ni];
-            if (depth > 16 || !n.live || !n.type) return false;
-            if (n.type->emit == emit_fm_operator) return port == "output" && finite_op(ni, depth + 1, guards);
-            if (n.type->emit == emit_crossfade && xfades.count(ni)) { // output_a: the input; output_b: +-0
-                const auto r = src_ref(n, "input");
-                return port == "output_b" || (port == "output_a" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards));
-            }
-            if (n.type->emit == emit_mixer && mixers.count(ni)) {
-                const auto r = src_ref(n, dropped_in(n, "input_b") ? "input_a" : "input_b");
-                return port == "output" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards);
-            }
-            return false;
-        };
-        finite_op = [&](int ni, int depth, std::set<int>* guards) {
-            const NodeInst& n = cg.nodes[ni];
-            if (!usable(n, emit_fm_operator)) return false;
-            auto def_of = [&](const char* port) {
-                for (const auto& ps : n.type->inputs)
-                    if (!strcmp(ps.name, port)) return (ps.arg >= 0 && (size_t)ps.arg < n.decl->args.size()) ? n.decl->args[ps.arg] : ps.def;
-                return NAN;
-            };
-            if (n.in_edges.count("envelope")) {
-                const auto r = src_ref(n, "envelope");
-                if (r.first < 0 || r.second != "output" || !usable(cg.nodes[r.first], emit_adsr)) return false;
-            } else if (!std::isfinite(def_of("envelope"))) {
-                return false;
-            }
-            const int ls = cg.fm_level_slot.count(n.id) ? cg.fm_level_slot[n.id] : -1;
-            if (ls == -1) return false;
-            if (ls >= 0 && guards) guards->insert(ls);
-            if (n.in_edges.count("feedback") ? !fb_ops.count(ni) : def_of("feedback") != 0.0f) return false;
-            if (!n.in_edges.count("phase_mod")) return (bool)std::isfinite(def_of("phase_mod"));
-            const auto r = src_ref(n, "phase_mod");
-            return r.first >= 0 && finite_src(r.first, r.second, depth, guards);
-        };
-        // every edge that reads `port` of node n is a plain, same-rate edge into an FmOperator's phase_mod or -- where a Mixer may
-        // follow -- into an input of a Mixer that is still a candidate; no fan-in at the consumer, no feedback, no policy
-        auto feeds_only = [&](const NodeInst& n, bool mixer_ok) {
-            for (const GEdge& e : g.edges) {
-                if (!count_node_refs(e.src, n.decl->name)) continue;
-                const std::string sp = strip_ws(e.src);
-                const size_t sdot = sp.rfind('.'), dot = e.dst.rfind('.');
-                if (sdot == std::string::npos || sp.substr(0, sdot) != n.decl->name || dot == std::string::npos || e.feedback || !e.policy.empty())
-                    return false;
-                if (cg.fb_sources.count("n" + std::to_string(n.id) + "." + sp.substr(sdot + 1))) return false;
-                auto ti = cg.node_by_name.find(e.dst.substr(0, dot));
-                if (ti == cg.node_by_name.end()) return false;
-                const NodeInst& t = cg.nodes[ti->second];
-                const std::string tp = e.dst.substr(dot + 1);
-                auto te = t.in_edges.find(tp);
-                if (!t.live || t.domain != n.domain || te == t.in_edges.end() || te->second.size() != 1) return false;
-                const bool to_op = usable(t, emit_fm_operator) && tp == "phase_mod";
-                const bool to_mixer = mixer_ok && mixers.count(ti->second) && (tp == "input_a" || tp == "input_b");
-                if (!to_op && !to_mixer) return false;
-            }
-            return true;
-        };
-        for (bool changed = true; changed;) {
-            changed = false;
-            auto thin = [&](std::set<int>& set, const std::function<bool(int)>& ok) {
-                for (auto it = set.begin(); it != set.end();)
-                    if (!ok(*it)) {
-                        it = set.erase(it);
-                        changed = true;
-                    } else {
-                        ++it;
-                    }
-            };
-            thin(fb_ops, [&](int ni) { return finite_op(ni, 0, nullptr); });
-            thin(xfades, [&](int ni) {
-                const auto r = src_ref(cg.nodes[ni], "input");
-                return r.first >= 0 && finite_src(r.first, r.second, 0, nullptr) && feeds_only(cg.nodes[ni], true);
-            });
-            thin(mixers, [&](int ni) {
-                const NodeInst& m = cg.nodes[ni];
-                return (dropped_in(m, "input_a") || dropped_in(m, "input_b")) && feeds_only(m, false);
-            });
-        }
-        std::set<int> guards, zeros(out.zero_slots.begin(), out.zero_slots.end());
-        for (int ni : fb_ops) {
-            (void)finite_op(ni, 0, &guards);
-            zeros.insert(cg.fm_fb_slot[cg.nodes[ni].id]);
-            z2set.insert(cg.nodes[ni].id);
-        }
-        for (int ni : xfades) {
-            const auto r = src_ref(cg.nodes[ni], "input");
-            (void)finite_src(r.first, r.second, 0, &guards);
-            zeros.insert(cg.xfade_mix_slot[cg.nodes[ni].id]);
-            z2set.insert(cg.nodes[ni].id);
-        }
-        for (int ni : mixers) z2set.insert(cg.nodes[ni].id);
-        if (!z2set.empty()) {
-            // (the same layout check as the zero variant's: without it the graph simply has no such unit)
-            std::set<int> all = zset;
-            all.insert(z2set.begin(), z2set.end());
-            bool same = false;
-            try {
-                const auto z = compile_pass(g_in, &all, &z2body);
-                same = z->n_slots == out.n_slots && z->state.size() == out.state.size() && z->n_ramps == out.n_ramps &&
-                       z->n_streams == out.n_streams && z->lpv == out.lpv && z->max_pipeline == out.max_pipeline && z->wide4 == out.wide4;
-                for (size_t i = 0; same && i < out.state.size(); ++i) same = z->state[i].name == out.state[i].name;
-            } catch (const std::exception&) {
-                same = false;
-            }
-            if (same) {
-                out.zero2_slots.assign(zeros.begin(), zeros.end());
-                out.finite_slots.assign(guards.begin(), guards.end());
-            } else {
-                z2set.clear();
-                z2body.clear();
-            }
-        }
+        if (usable(d, emit_fm_operator) && slot_of(cg.fm_fb_slot) >= 0) fb_ops.insert(cg.node_by_name.at(d.decl->name));
+        if (usable(d, emit_crossfade) && slot_of(cg.xfade_mix_slot) >= 0) xfades.insert(cg.node_by_name.at(d.decl->name));
+        if (usable(d, emit_mixer)) mixers.insert(cg.node_by_name.at(d.decl->name));
     }
+    // the one plain `node.port` source of an input: (node index, port); (-1, "") for anything else -- an unconnected input,
+    // an expression, a fan-in, a policy edge
+    auto src_ref = [&](const NodeInst& n, const std::string& port) -> std::pair<int, std::string> {
+        auto it = n.in_edges.find(port);
+        if (it == n.in_edges.end() || it->second.size() != 1) return {-1, ""};
+        const NodeInst::Src& sr = it->second[0];
+        if (!sr.policy.empty() || sr.e->t != Expr::Ref || sr.e->port.empty()) return {-1, ""};
+        auto ni = cg.node_by_name.find(sr.e->node);
+        if (ni == cg.node_by_name.end() || cg.nodes[ni->second].domain != n.domain) return {-1, ""};
+        return {ni->second, sr.e->port};
+    };
+    auto dropped_in = [&](const NodeInst& m, const char* port) { // a Mixer input that reads a folded Crossfade's output_b
+        const auto r = src_ref(m, port);
+        return r.first >= 0 && r.second == "output_b" && xfades.count(r.first) > 0;
+    };
+    // An operator whose output is finite on every frame, given finite levels: sin and an ADSR level are bounded, the level is
+    // a finite literal or a slot the engine tests (`guards`), and nothing non-finite can reach the sine -- the feedback term
+    // is absent or folded, the phase modulation comes from such operators through folded nodes only.
+    std::function<bool(int, int, std::set<int>*)> finite_op;
+    std::function<bool(int, const std::string&, int, std::set<int>*)> finite_src = [&](int ni, const std::string& port, int depth, std::set<int>* guards) {
+        const NodeInst& n = cg.nodes[ni];
+        if (depth > 16 || !n.live || !n.type) return false;
+        if (n.type->emit == emit_fm_operator) return port == "output" && finite_op(ni, depth + 1, guards);
+        if (n.type->emit == emit_crossfade && xfades.count(ni)) { // output_a: the input; output_b: +-0
+            const auto r = src_ref(n, "input");
+            return port == "output_b" || (port == "output_a" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards));
+        }
+        if (n.type->emit == emit_mixer && mixers.count(ni)) {
+            const auto r = src_ref(n, dropped_in(n, "input_b") ? "input_a" : "input_b");
+            return port == "output" && r.first >= 0 && finite_src(r.first, r.second, depth + 1, guards);
+        }
+        return false;
+    };
+    finite_op = [&](int ni, int depth, std::set<int>* guards) {
+        const NodeInst& n = cg.nodes[ni];
+        if (!usable(n, emit_fm_operator)) return false;
+        auto def_of = [&](const char* port) {
+            for (const auto& ps : n.type->inputs)
+                if (!strcmp(ps.name, port)) return (ps.arg >= 0 && (size_t)ps.arg < n.decl->args.size()) ? n.decl->args[ps.arg] : ps.def;
+            return NAN;
+        };
+        if (n.in_edges.count("envelope")) {
+            const auto r = src_ref(n, "envelope");
+            if (r.first < 0 || r.second != "output" || !usable(cg.nodes[r.first], emit_adsr)) return false;
+        } else if (!std::isfinite(def_of("envelope"))) {
+            return false;
+        }
+        const int ls = cg.fm_level_slot.count(n.id) ? cg.fm_level_slot[n.id] : -1;
+        if (ls == -1) return false;
+        if (ls >= 0 && guards) guards->insert(ls);
+        if (n.in_edges.count("feedback") ? !fb_ops.count(ni) : def_of("feedback") != 0.0f) return false;
+        if (!n.in_edges.count("phase_mod")) return (bool)std::isfinite(def_of("phase_mod"));
+        const auto r = src_ref(n, "phase_mod");
+        return r.first >= 0 && finite_src(r.first, r.second, depth, guards);
+    };
+    // every edge that reads `port` of node n is a plain, same-rate edge into an FmOperator's phase_mod or -- where a Mixer may
+    // follow -- into an input of a Mixer that is still a candidate; no fan-in at the consumer, no feedback, no policy
+    auto feeds_only = [&](const NodeInst& n, bool mixer_ok) {
+        for (const GEdge& e : g.edges) {
+            if (!count_node_refs(e.src, n.decl->name)) continue;
+            const std::string sp = strip_ws(e.src);
+            const size_t sdot = sp.rfind('.'), dot = e.dst.rfind('.');
+            if (sdot == std::string::npos || sp.substr(0, sdot) != n.decl->name || dot == std::string::npos || e.feedback || !e.policy.empty())
+                return false;
+            if (cg.fb_sources.count("n" + std::to_string(n.id) + "." + sp.substr(sdot + 1))) return false;
+            auto ti = cg.node_by_name.find(e.dst.substr(0, dot));
+            if (ti == cg.node_by_name.end()) return false;
+            const NodeInst& t = cg.nodes[ti->second];
+            const std::string tp = e.dst.substr(dot + 1);
+            auto te = t.in_edges.find(tp);
+            if (!t.live || t.domain != n.domain || te == t.in_edges.end() || te->second.size() != 1) return false;
+            const bool to_op = usable(t, emit_fm_operator) && tp == "phase_mod";
+            const bool to_mixer = mixer_ok && mixers.count(ti->second) && (tp == "input_a" || tp == "input_b");
+            if (!to_op && !to_mixer) return false;
+        }
+        return true;
+    };
+    for (bool changed = true; changed;) {
+        changed = false;
+        auto thin = [&](std::set<int>& set, const std::function<bool(int)>& ok) {
+            for (auto it = set.begin(); it != set.end();)
+                if (!ok(*it)) {
+                    it = set.erase(it);
+                    changed = true;
+                } else {
+                    ++it;
+                }
+        };
+        thin(fb_ops, [&](int ni) { return finite_op(ni, 0, nullptr); });
+        thin(xfades, [&](int ni) {
+            const auto r = src_ref(cg.nodes[ni], "input");
+            return r.first >= 0 && finite_src(r.first, r.second, 0, nullptr) && feeds_only(cg.nodes[ni], true);
+        });
+        thin(mixers, [&](int ni) {
+            const NodeInst& m = cg.nodes[ni];
+            return (dropped_in(m, "input_a") || dropped_in(m, "input_b")) && feeds_only(m, false);
+        });
+    }
+    std::set<int> guards, zeros(out.zero_slots.begin(), out.zero_slots.end());
+    for (int ni : fb_ops) {
+        (void)finite_op(ni, 0, &guards);
+        zeros.insert(cg.fm_fb_slot[cg.nodes[ni].id]);
+        z2set.insert(cg.nodes[ni].id);
+    }
+    for (int ni : xfades) {
+        const auto r = src_ref(cg.nodes[ni], "input");
+        (void)finite_src(r.first, r.second, 0, &guards);
+        zeros.insert(cg.xfade_mix_slot[cg.nodes[ni].id]);
+        z2set.insert(cg.nodes[ni].id);
+    }
+    for (int ni : mixers) z2set.insert(cg.nodes[ni].id);
+    return {z2set, zeros, guards};
+}
+
+// ---- the translation units: the general kernels' (csrc/gen/<graph>.hip) and the zero variants' (<graph>_z.hip, _z2.hip) ------
+// a unit from its first line to the end of its namespace; `desc` is what its head comment says after the GENERATED line
+void write_unit_head(std::ostringstream& os, const std::string& graph, const std::string& desc, const std::string& pre, const std::string& ns, int lpv,
+                     const std::string& body)
+{
+    os << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << graph << "' -- do not edit.\n"
+       << desc << pre << "namespace " << ns << " {\nconstexpr int LPV = " << lpv << "; // lanes per voice\n"
+       << body << "} // namespace\n\n"
+       << "#undef SF\n#undef SU\n#undef RV\n#undef ST\n#undef RVP\n#undef STP\n\n";
+}
+
+void write_kernel_entry(std::ostringstream& os, int threads, const std::string& attr, const std::string& kernel, const std::string& fn,
+                        const std::string& targs)
+{
+    os << "extern \"C\" __global__ __launch_bounds__(" << threads << ")" << attr << " void " << kernel << "(OgBlockArgs A) { " << fn << "<" << targs
+       << ">(A); }\n";
+}
+
+// the launch of one kernel shape (`kernel`: its name up to and including the hash) by ramps and taps; a zero variant's unit
+// (sfx) has the two kernels that read no ramp table only
+void write_dispatch(std::ostringstream& os, const char* ind, const std::string& kernel, const char* sfx, const char* dims)
+{
+    if (sfx) {
+        os << ind << "if (taps) hipLaunchKernelGGL(" << kernel << "_01" << sfx << ", " << dims << ", 0, s, A);\n"
+           << ind << "else hipLaunchKernelGGL(" << kernel << "_00" << sfx << ", " << dims << ", 0, s, A);\n";
+        return;
+    }
+    os << ind << "if (!ramps && !taps) hipLaunchKernelGGL(" << kernel << "_00, " << dims << ", 0, s, A);\n"
+       << ind << "else if (ramps && !taps) hipLaunchKernelGGL(" << kernel << "_10, " << dims << ", 0, s, A);\n"
+       << ind << "else if (!ramps && taps) hipLaunchKernelGGL(" << kernel << "_01, " << dims << ", 0, s, A);\n"
+       << ind << "else hipLaunchKernelGGL(" << kernel << "_11, " << dims << ", 0, s, A);\n";
+}
+
+void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbody, const std::set<int>& z2set, const std::string& z2body)
+{
+    const GraphDesc& g = gen.g;
+    CompiledGraph& out = *gen.out;
+    const Codegen& cg = gen.cg;
     // the wide four-wave form: 16-frame chunks, flag hand-off over rings of two chunks (round 6; round 5: one barrier per chunk).
     // OGC_FLAGS="xch,depth" (experiment): `xch` frames per chunk, rings of `depth` chunks, depth 0 = the barrier
     std::string wide_args = "16, 2";
@@ -5198,27 +5472,51 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         if (sscanf(ef, "%d,%d", &xch, &fd) == 2 && (xch == 4 || xch == 8 || xch == 16) && (fd == 0 || (fd >= 2 && fd <= 8)))
             wide_args = std::to_string(xch) + ", " + std::to_string(fd);
     }
-    out.hash = fnv1a(body_s + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
+    out.hash = fnv1a(gen.body + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
                      "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()) +
                      (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST));
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
 
-    std::ostringstream src;
-    src << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << g.name << "' -- do not edit.\n"
-        << "// One fused voice kernel: " << out.state.size() << " state words/voice, " << out.n_slots
-        << " uniform slots, " << out.n_ramps << " ramped inputs, " << out.n_event_inputs << " event inputs"
-        << (out.lpv > 1 ? ", " + std::to_string(out.lane_state.size()) + " arrays x " + std::to_string(out.lpv) + " lanes x " +
-                              std::to_string(out.lane_width) + " words/voice"
-                        : std::string())
-        << ".\n"
-        << "// Node order: ";
+    struct Unit { // the general unit (sfx null) and the zero variants' (suffix of the kernel names and of the namespace)
+        const char* sfx = nullptr;
+        bool on = true;
+        std::ostringstream os;
+        std::string tail() const { return sfx ? std::string("_") + sfx : std::string(); }
+    } units[3];
+    units[1].sfx = "z";
+    units[1].on = !zbody.empty();
+    units[2].sfx = "z2";
+    units[2].on = !z2body.empty();
+
+    std::ostringstream desc, zdesc, z2desc;
+    desc << "// One fused voice kernel: " << out.state.size() << " state words/voice, " << out.n_slots
+         << " uniform slots, " << out.n_ramps << " ramped inputs, " << out.n_event_inputs << " event inputs"
+         << (out.lpv > 1 ? ", " + std::to_string(out.lane_state.size()) + " arrays x " + std::to_string(out.lpv) + " lanes x " +
+                               std::to_string(out.lane_width) + " words/voice"
+                         : std::string())
+         << ".\n"
+         << "// Node order: ";
     if (out.node_order.empty()) out.node_order = out.schedule_order; // (not reordered: emitted in the reference's order)
-    for (auto& nn : out.node_order) src << nn << " ";
+    for (auto& nn : out.node_order) desc << nn << " ";
     if (out.schedule_order != out.node_order) {
-        src << "\n// Schedule (depth first from the sinks; same values, any topological order of a pure dataflow graph): ";
-        for (auto& nn : out.schedule_order) src << nn << " ";
+        desc << "\n// Schedule (depth first from the sinks; same values, any topological order of a pure dataflow graph): ";
+        for (auto& nn : out.schedule_order) desc << nn << " ";
     }
+    zdesc << "// The zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroChain): the same kernel for launches in which slot(s)";
+    for (int zs : out.zero_slots) zdesc << " " << zs;
+    zdesc << " hold +-0\n// and no ramp ticks.  Left out:";
+    for (const NodeInst& n : cg.nodes)
+        if (zset.count(n.id)) zdesc << " " << n.decl->name;
+    zdesc << " (their consumers read the AddValue's value from its slot).";
+    z2desc << "// The deeper zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroFolds): the same kernel for launches in which slot(s)";
+    for (int zs : out.zero2_slots) z2desc << " " << zs;
+    z2desc << " hold +-0,\n// slot(s)";
+    for (int fs : out.finite_slots) z2desc << " " << fs;
+    z2desc << " are finite and no ramp ticks.  Left out or folded:";
+    for (const NodeInst& n : cg.nodes)
+        if (zset.count(n.id) || z2set.count(n.id)) z2desc << " " << n.decl->name;
+    z2desc << ".";
     // (the preamble of a unit: the zero variant's unit has the same one)
     std::ostringstream pre;
     if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
@@ -5232,47 +5530,11 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         << "// the pipelined kernels: the chunk's rows are in rv_<row>[] when the chunk body is the unrolled one (BoolC::pre)\n"
         << "#define RVP(row, slot) (RAMPS ? og::row_pick<decltype(chk)::pre>(rv_##row, j, A, (row), f) : og::slot_f(A, (slot)))\n"
         << "#define STP(row) og::row_pick<decltype(chk)::pre>(rv_##row, j, A, (row), f)\n\n";
-    const char* undefs = "#undef SF\n#undef SU\n#undef RV\n#undef ST\n#undef RVP\n#undef STP\n\n";
-    src << pre.str()
-        << "namespace og_gen_" << hs << " {\n"
-        << "constexpr int LPV = " << out.lpv << "; // lanes per voice\n"
-        << body_s << "} // namespace\n\n" << undefs;
-    // the zero variant's unit (csrc/gen/<graph>_z.hip)
-    const bool zv = !zbody.empty();
-    std::ostringstream zsrc;
-    if (zv) {
-        zsrc << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << g.name << "' -- do not edit.\n"
-             << "// The zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroChain): the same kernel for launches in which slot(s)";
-        for (int zs : out.zero_slots) zsrc << " " << zs;
-        zsrc << " hold +-0\n// and no ramp ticks.  Left out:";
-        for (const NodeInst& n : cg.nodes)
-            if (zset.count(n.id)) zsrc << " " << n.decl->name;
-        zsrc << " (their consumers read the AddValue's value from its slot)." << pre.str() << "namespace og_gen_" << hs
-             << "_z {\nconstexpr int LPV = " << out.lpv << "; // lanes per voice\n" << zbody << "} // namespace\n\n" << undefs;
-    }
-    // the deeper zero variant's unit (csrc/gen/<graph>_z2.hip)
-    const bool zv2 = !z2body.empty();
-    std::ostringstream z2src;
-    if (zv2) {
-        z2src << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << g.name << "' -- do not edit.\n"
-              << "// The deeper zero variant of og_gen_" << hs << " (og_graph.cpp, ZeroFolds): the same kernel for launches in which slot(s)";
-        for (int zs : out.zero2_slots) z2src << " " << zs;
-        z2src << " hold +-0,\n// slot(s)";
-        for (int fs : out.finite_slots) z2src << " " << fs;
-        z2src << " are finite and no ramp ticks.  Left out or folded:";
-        for (const NodeInst& n : cg.nodes)
-            if (zset.count(n.id) || z2set.count(n.id)) z2src << " " << n.decl->name;
-        z2src << "." << pre.str() << "namespace og_gen_" << hs << "_z2 {\nconstexpr int LPV = " << out.lpv << "; // lanes per voice\n" << z2body
-              << "} // namespace\n\n" << undefs;
-    }
-    // (the units of the zero variants: stream, suffix of the kernel names and of the namespace)
-    struct ZUnit {
-        std::ostringstream* os;
-        const char* sfx;
-    };
-    std::vector<ZUnit> zunits;
-    if (zv) zunits.push_back({&zsrc, "z"});
-    if (zv2) zunits.push_back({&z2src, "z2"});
+    const std::string ns = std::string("og_gen_") + hs;
+    write_unit_head(units[0].os, g.name, desc.str(), pre.str(), ns, out.lpv, gen.body);
+    if (units[1].on) write_unit_head(units[1].os, g.name, zdesc.str(), pre.str(), ns + "_z", out.lpv, zbody);
+    if (units[2].on) write_unit_head(units[2].os, g.name, z2desc.str(), pre.str(), ns + "_z2", out.lpv, z2body);
+
     const char* variants[4][3] = {{"00", "false", "false"}, {"10", "true", "false"}, {"01", "false", "true"},
                                   {"11", "true", "true"}};
     // register budget of the ordinary kernel: 4 waves per SIMD = 128 VGPRs.  The 4-lanes-per-voice e-piano form
@@ -5290,19 +5552,17 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         if (player_channels > 2) waves_eu = 2;
     }
     if (const char* ew = ogabi::experiment_knob("OGC_WAVES_EU")) waves_eu = std::max(1, std::min(8, atoi(ew)));
-    // the zero variant: only next to the kernels that read no ramp table (`_00z`, `_01z`)
-    auto zero_variants = [&](const std::function<void(std::ostringstream& zsrc, const char* z, const char* v, const char* taps)>& f) {
-        for (auto& u : zunits)
+    // the entry points of one kernel shape (`kp`: the kernel name up to the hash): the four ramps / taps variants in the general
+    // unit; a zero variant only next to the kernels that read no ramp table (`_00z`, `_01z`)
+    auto shape = [&](const std::string& kp, const std::string& fn, int threads, const std::string& attr, const std::string& zattr, const std::string& extra) {
+        for (Unit& u : units)
             for (auto& v : variants)
-                if (v[1][0] == 'f') f(*u.os, u.sfx, v[0], v[2]);
+                if (u.on && !(u.sfx && v[1][0] != 'f'))
+                    write_kernel_entry(u.os, threads, u.sfx ? zattr : attr, kp + hs + "_" + v[0] + (u.sfx ? u.sfx : ""), ns + u.tail() + "::" + fn,
+                                       std::string(u.sfx ? "false" : v[1]) + ", " + v[2] + extra);
     };
-    for (auto& v : variants)
-        src << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v[0]
-            << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block<" << v[1] << ", " << v[2] << ">(A); }\n";
-    zero_variants([&](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
-        zsrc << "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" << waves_eu << "))) void og_k_" << hs << "_" << v
-            << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block<false, " << taps << ">(A); }\n";
-    });
+    const std::string budget = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_eu) + ")))";
+    shape("og_k_", "voice_block", 64, budget, budget, "");
     std::vector<std::pair<int, int>> depths; // (tag: what OgBlockArgs::split selects, waves per workgroup)
     if (!cg.groups2.empty()) depths.push_back({2, (int)cg.groups2.size()});
     if (!cg.groups4.empty()) depths.push_back({4, (int)cg.groups4.size()});
@@ -5313,74 +5573,41 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
         if (fd >= 2 && fd <= 8) narrow_args = ", 8, " + std::to_string(fd);
     }
     for (auto [K, W] : depths) {
-        for (auto& v : variants)
-            src << "extern \"C\" __global__ __launch_bounds__(" << 64 * W << ") void og_k" << K << "_" << hs << "_" << v[0]
-                << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block_p" << K << "<" << v[1] << ", " << v[2] << narrow_args << ">(A); }\n";
         // (the narrow four-wave form holds six workgroups per CU; left to itself the compiler gives the zero kernel 82 VGPRs
         // where the general one has 80 -- five waves per SIMD.  Held to six: 72 VGPRs, no spill)
         const std::string zbudget = (K == 4 && narrow_args.empty()) ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
-        zero_variants([&, K = K, W = W](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
-            zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * W << ")" << zbudget << " void og_k" << K << "_" << hs << "_" << v
-                << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block_p" << K << "<false, " << taps << narrow_args << ">(A); }\n";
-        });
+        shape("og_k" + std::to_string(K) + "_", "voice_block_p" + std::to_string(K), 64 * W, "", zbudget, narrow_args);
     }
-    if (out.wide4) {
-        for (auto& v : variants)
-            src << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v[0]
-                << "(OgBlockArgs A) { og_gen_" << hs << "::voice_block_p4<" << v[1] << ", " << v[2] << ", " << wide_args << ">(A); }\n";
-        zero_variants([&](std::ostringstream& zsrc, const char* z, const char* v, const char* taps) {
-            zsrc << "extern \"C\" __global__ __launch_bounds__(" << 64 * (int)cg.groups4.size() << ") void og_k4w_" << hs << "_" << v
-                << z << "(OgBlockArgs A) { og_gen_" << hs << "_" << z << "::voice_block_p4<false, " << taps << ", " << wide_args << ">(A); }\n";
-        });
-    }
-    src << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
-        << "static void og_launch_" << hs << "(const OgBlockArgs& A, bool ramps, bool taps, hipStream_t s)\n{\n"
-        << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
-    for (auto& u : zunits)
-        *u.os << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
-              << "static void og_launch_" << hs << "_" << u.sfx << "(const OgBlockArgs& A, bool taps, hipStream_t s)\n{\n"
-              << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
-    // the zero variant's launch of a shape (`kp`: the kernel name up to the hash), inside its `if (A.split ...) {`
-    auto zero_branch = [&](const std::string& kp, const char* dims, const std::string& head) {
-        for (auto& u : zunits)
-            *u.os << head << "        if (taps) hipLaunchKernelGGL(" << kp << hs << "_01" << u.sfx << ", " << dims << ", 0, s, A);\n"
-                  << "        else hipLaunchKernelGGL(" << kp << hs << "_00" << u.sfx << ", " << dims << ", 0, s, A);\n"
-                  << (head.empty() ? "" : "        return;\n    }\n");
+    if (out.wide4) shape("og_k4w_", "voice_block_p4", 64 * (int)cg.groups4.size(), "", "", ", " + wide_args);
+
+    for (Unit& u : units)
+        if (u.on)
+            u.os << "\n#ifndef OG_JIT\n#include \"og_registry.h\"\n"
+                 << "static void og_launch_" << hs << u.tail() << "(const OgBlockArgs& A, " << (u.sfx ? "" : "bool ramps, ") << "bool taps, hipStream_t s)\n{\n"
+                 << "    const dim3 grid(((size_t)A.n_voices * " << out.lpv << " + A.lanes - 1) / A.lanes), block(OG_WAVE);\n";
+    // the launch of a pipelined shape, inside its `if (A.split ...) {`
+    auto branch = [&](const std::string& cond, size_t waves, const std::string& kp) {
+        for (Unit& u : units) {
+            if (!u.on) continue;
+            u.os << "    if (" << cond << "\n"
+                 << "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" << waves << " * OG_WAVE);\n";
+            write_dispatch(u.os, "        ", kp + hs, u.sfx, "gk, bk");
+            u.os << "        return;\n    }\n";
+        }
     };
-    if (out.wide4) {
-        const std::string head = std::string("    if (A.split == 4u && A.wide) { // four waves per 64 voices, 16-frame hand-offs\n") +
-                                 "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" + std::to_string(cg.groups4.size()) + " * OG_WAVE);\n";
-        src << head;
-        zero_branch("og_k4w_", "gk, bk", head);
-        src << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k4w_" << hs << "_00, gk, bk, 0, s, A);\n"
-            << "        else if (ramps && !taps) hipLaunchKernelGGL(og_k4w_" << hs << "_10, gk, bk, 0, s, A);\n"
-            << "        else if (!ramps && taps) hipLaunchKernelGGL(og_k4w_" << hs << "_01, gk, bk, 0, s, A);\n"
-            << "        else hipLaunchKernelGGL(og_k4w_" << hs << "_11, gk, bk, 0, s, A);\n"
-            << "        return;\n    }\n";
+    if (out.wide4) branch("A.split == 4u && A.wide) { // four waves per 64 voices, 16-frame hand-offs", cg.groups4.size(), "og_k4w_");
+    for (auto [K, W] : depths)
+        branch("A.split == " + std::to_string(K) + "u) { // " + std::to_string(W) + " waves per 64 voices", (size_t)W, "og_k" + std::to_string(K) + "_");
+    for (Unit& u : units) {
+        if (!u.on) continue;
+        write_dispatch(u.os, "    ", std::string("og_k_") + hs, u.sfx, "grid, block");
+        u.os << "}\n";
+        if (u.sfx) // (the deeper variant is the registry's tier 2; the zero variant registers as tier 1)
+            u.os << "static const OgZeroKernelRegistrar og_" << u.sfx << "reg_" << hs << "(0x" << hs << "ull, &og_launch_" << hs << u.tail()
+                 << (!strcmp(u.sfx, "z2") ? ", 2" : "") << ");\n#endif\n";
     }
-    for (auto [K, W] : depths) {
-        const std::string head = "    if (A.split == " + std::to_string(K) + "u) { // " + std::to_string(W) + " waves per 64 voices\n" +
-                                 "        const dim3 gk((A.n_voices + OG_WAVE - 1) / OG_WAVE), bk(" + std::to_string(W) + " * OG_WAVE);\n";
-        src << head;
-        zero_branch("og_k" + std::to_string(K) + "_", "gk, bk", head);
-        src << "        if (!ramps && !taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_00, gk, bk, 0, s, A);\n"
-            << "        else if (ramps && !taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_10, gk, bk, 0, s, A);\n"
-            << "        else if (!ramps && taps) hipLaunchKernelGGL(og_k" << K << "_" << hs << "_01, gk, bk, 0, s, A);\n"
-            << "        else hipLaunchKernelGGL(og_k" << K << "_" << hs << "_11, gk, bk, 0, s, A);\n"
-            << "        return;\n    }\n";
-    }
-    for (auto& u : zunits) {
-        const bool deep = !strcmp(u.sfx, "z2"); // (the registry's tier 2; the zero variant registers as tier 1)
-        *u.os << "    if (taps) hipLaunchKernelGGL(og_k_" << hs << "_01" << u.sfx << ", grid, block, 0, s, A);\n"
-              << "    else hipLaunchKernelGGL(og_k_" << hs << "_00" << u.sfx << ", grid, block, 0, s, A);\n}\n"
-              << "static const OgZeroKernelRegistrar og_" << u.sfx << "reg_" << hs << "(0x" << hs << "ull, &og_launch_" << hs << "_" << u.sfx
-              << (deep ? ", 2" : "") << ");\n#endif\n";
-    }
-    src <<"    if (!ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_00, grid, block, 0, s, A);\n"
-        << "    else if (ramps && !taps) hipLaunchKernelGGL(og_k_" << hs << "_10, grid, block, 0, s, A);\n"
-        << "    else if (!ramps && taps) hipLaunchKernelGGL(og_k_" << hs << "_01, grid, block, 0, s, A);\n"
-        << "    else hipLaunchKernelGGL(og_k_" << hs << "_11, grid, block, 0, s, A);\n}\n"
-        << "static int og_occ_" << hs << "(int depth) // resident workgroups per CU of each shape (registers, LDS)\n{\n    int n = 0;\n";
+    std::ostringstream& src = units[0].os;
+    src << "static int og_occ_" << hs << "(int depth) // resident workgroups per CU of each shape (registers, LDS)\n{\n    int n = 0;\n";
     for (auto [K, W] : depths)
         src << "    if (depth == " << K << ") { (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, og_k" << K << "_" << hs << "_00, " << 64 * W
             << ", 0); return n; }\n";
@@ -5390,10 +5617,37 @@ std::unique_ptr<CompiledGraph> compile_pass(const GraphDesc& g_in, const std::se
     src << "    if (depth <= 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, og_k_" << hs << "_00, OG_WAVE, 0);\n    return n;\n}\n"
         << "static const OgKernelRegistrar og_reg_" << hs << "(0x" << hs << "ull, \"" << g.name << "\", &og_launch_"
         << hs << ", &og_occ_" << hs << ");\n#endif\n";
-    out.source = src.str();
-    out.zero_source = zsrc.str();
-    out.zero2_source = z2src.str();
-    return cgp;
+    out.source = units[0].os.str();
+    out.zero_source = units[1].os.str();
+    out.zero2_source = units[2].os.str();
+}
+
+} // namespace
+
+// The general pass first; the `_z` pass before the `_z2` set is computed (find_zero_folds reads out.zero_slots); the `_z2`
+// pass folds both sets.
+std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
+{
+    const auto gen = lower(g_in, nullptr);
+    CompiledGraph& out = *gen->out;
+    std::set<int> zset = find_zero_chain(*gen);
+    const std::string zbody = lower_variant(g_in, zset, out);
+    if (zbody.empty()) {
+        zset.clear();
+        out.zero_slots.clear();
+    }
+    ZeroFolds z2 = find_zero_folds(*gen);
+    std::set<int> all = zset;
+    all.insert(z2.nodes.begin(), z2.nodes.end());
+    const std::string z2body = lower_variant(g_in, z2.nodes.empty() ? z2.nodes : all, out);
+    if (z2body.empty()) {
+        z2.nodes.clear();
+    } else {
+        out.zero2_slots.assign(z2.zeros.begin(), z2.zeros.end());
+        out.finite_slots.assign(z2.guards.begin(), z2.guards.end());
+    }
+    write_units(*gen, zset, zbody, z2.nodes, z2body);
+    return std::move(gen->out);
 }
 
 } // namespace ogc
