@@ -222,6 +222,14 @@ pub const OG_SAMPLE_NONE: u32 = 0xFFFF_FFFF;
 extern "C" {
     pub fn og_register_sample(name: *const c_char, interleaved: *const c_float, frames: u64, channels: u32) -> c_int;
     pub fn og_unregister_sample(name: *const c_char) -> c_int;
+    pub fn og_register_sample_at_rate(name: *const c_char, interleaved: *const c_float, frames: u64, channels: u32,
+                                      sample_rate: u32) -> c_int;
+    pub fn og_register_sample_wav(name: *const c_char, path: *const c_char) -> c_int;
+    pub fn og_sample_info(name: *const c_char, frames: *mut u64, channels: *mut u32, sample_rate: *mut u32) -> c_int;
+    pub fn og_read_sample(name: *const c_char, out: *mut c_float, capacity_frames: u64) -> c_int;
+    pub fn og_resample_frames(frames: u64, src_rate: u32, dst_rate: u32, out_frames: *mut u64) -> c_int;
+    pub fn og_resample(interleaved: *const c_float, frames: u64, channels: u32, src_rate: u32, dst_rate: u32,
+                       out: *mut c_float, out_capacity_frames: u64) -> c_int;
     pub fn og_load_sample(e: *mut og_engine, name: *const c_char, index: *mut u32) -> c_int;
     pub fn og_set_sample(e: *mut og_engine, node: *const c_char, index: u32) -> c_int;
     pub fn og_set_voice_samples(e: *mut og_engine, node: *const c_char, first_voice: u32, count: u32,

@@ -1,10 +1,12 @@
 """Render a small multisample bank -- every voice loops its own synthesised sample through an envelope -- and write a WAV.
 
     python examples/render_multisample.py [out.wav]
+    python examples/render_multisample.py --out out.wav kick.wav snare.wav ...
 
 register_sample -> Engine.load_sample -> Engine.set_voice_samples: each voice's SamplePlayer reads its buffer from the engine's
-device sample pool; a gate event per voice opens its AdsrEnvelope.  No input file: the samples are synthesised here.  Needs an
-MI355X (there is no CPU fallback).
+device sample pool; a gate event per voice opens its AdsrEnvelope.  Without input files the samples are synthesised here; with
+WAV files on the command line (any rate: register_sample_wav keeps the file's rate and load_sample conforms it to the
+engine's on the device) the pattern plays those instead.  Needs an MI355X (there is no CPU fallback).
 """
 import os
 import sys
@@ -32,13 +34,18 @@ def tone(midi_note, cycles=64):
     return (0.6 * np.sin(2 * np.pi * t) + 0.25 * np.sin(4 * np.pi * t) + 0.15 * np.sin(6 * np.pi * t)).astype(np.float32)
 
 
-def main(path):
+def main(path, wavs=()):
     eng = oscen_amd.Engine(oscen_amd.Graph(dsl=VOICE), VOICES, sample_rate=float(SR))
     notes = [48, 52, 55, 60, 64, 67, 72, 76]
     index = []
-    for n in notes:
-        oscen_amd.register_sample("tone_%d" % n, tone(n))
-        index.append(eng.load_sample("tone_%d" % n))
+    for k, n in enumerate(notes):
+        if wavs:  # the files in turn, at their own rates
+            name = "wav_%d" % (k % len(wavs))
+            oscen_amd.register_sample_wav(name, wavs[k % len(wavs)])
+        else:
+            name = "tone_%d" % n
+            oscen_amd.register_sample(name, tone(n))
+        index.append(eng.load_sample(name))
     step = SR // 4  # a note every quarter of a second, two voices per note an octave of the pattern apart
     out = []
     for b in range((len(notes) * step + SR) // BLOCK):
@@ -62,4 +69,9 @@ def main(path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "multisample.wav")
+    args = sys.argv[1:]
+    if "--out" in args:
+        k = args.index("--out")
+        main(args[k + 1], args[:k] + args[k + 2:])
+    else:
+        main(args[0] if args else "multisample.wav")

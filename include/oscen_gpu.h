@@ -253,7 +253,9 @@ uint32_t og_active_ramps(const og_engine* e);
  * one: exactly 0.0 on every channel.  Every VOICE holds its own buffer choice and playhead (state fields `<node>.sample`,
  * `<node>.playhead` of og_read_state_field).  The reference binds the buffer through `external sample: AudioAsset;` and
  * `graph.sample.load_wav(path)`; here (the text front end refuses `external`) it is bound by name through the calls below:
- * register (decoding and rate conversion stay with the caller: samples are given at the graph's rate), load, set.
+ * register, load, set.  og_register_sample takes samples at the graph's rate; og_register_sample_at_rate and
+ * og_register_sample_wav keep the source's own rate, and og_load_sample conforms it to the graph rate on the device
+ * (AudioAsset::from_samples / from_wav, oscen-lib/src/asset/mod.rs:138-232).
  * Refused with OG_E_UNSUPPORTED: a player in an array-valued voice, in a node array, in a nested graph type, oversampled.
  *
  * Registry (process-wide, beside the impulse responses): interleaved frames, copied; channels 1..8; frames == 0 is legal
@@ -264,11 +266,38 @@ uint32_t og_active_ramps(const og_engine* e);
 #define OG_MAX_SAMPLE_FLOATS (1u << 28)
 int og_register_sample(const char* name, const float* interleaved, uint64_t frames, uint32_t channels);
 int og_unregister_sample(const char* name);
+/* The same at the source's own rate (the reference's AudioAsset::from_samples(.., rate, graph_rate)): og_load_sample conforms
+ * the sample to the engine's rate with the reference's offline windowed sinc (oscen-lib/src/asset/resample.rs: 32 zero
+ * crossings, Blackman window, widened by 1 / cutoff when downsampling, normalised by the weights applied) on the device, bit
+ * for bit the reference's result.  sample_rate == 0 (ZeroSampleRate) and frames == 0 (Empty) are OG_E_INVALID. */
+int og_register_sample_at_rate(const char* name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t sample_rate);
+/* Reads a RIFF/WAVE file (AudioAsset::from_wav) and registers it at the header's rate: PCM 16 / 24 / 32-bit (scaled by
+ * 1 / 2^(bits - 1)) and 32-bit IEEE float, plain or wrapped in WAVE_FORMAT_EXTENSIBLE.  Any other format (8-bit, ADPCM, ...)
+ * is OG_E_UNSUPPORTED; a malformed or truncated file is OG_E_INVALID with the reason in og_last_error. */
+int og_register_sample_wav(const char* name, const char* path);
+/* What the registry holds under a name: its shape and its rate (0: registered without one), and a copy of its interleaved
+ * frames as registered (og_sample_info's frames; OG_E_INVALID when capacity_frames is smaller).  Out-pointers of og_sample_info
+ * may be NULL. */
+int og_sample_info(const char* name, uint64_t* frames, uint32_t* channels, uint32_t* sample_rate);
+int og_read_sample(const char* name, float* out, uint64_t capacity_frames);
+/* The resampler by itself, on the current device, host buffers in and out -- e.g. to conform an impulse response before
+ * og_register_ir (the IR registry carries no rates).  og_resample_frames gives the output length, round(frames * dst / src);
+ * og_resample writes that many interleaved frames (OG_E_INVALID when out_capacity_frames is smaller).  Equal rates copy the
+ * input.  1..8 channels, frames >= 1, both rates > 0. */
+int og_resample_frames(uint64_t frames, uint32_t src_rate, uint32_t dst_rate, uint64_t* out_frames);
+int og_resample(const float* interleaved, uint64_t frames, uint32_t channels, uint32_t src_rate, uint32_t dst_rate, float* out,
+                uint64_t out_capacity_frames);
 /* Brings a registered sample onto the engine's device, once per width the graph's players have, with the channel mapping of
  * SamplePlayerConsumer::build (a 1-channel source broadcasts; otherwise player channel c takes source channel
  * min(c, channels - 1): a mono player takes channel 0, not a downmix), and hands out a stable engine-local index; loading a
  * name again returns the index it has.  Launches what is queued and waits for the device: not for the audio thread.  The
- * pool holds up to 2^32 floats (OG_E_NOMEM past that).  Samples stay loaded across og_init. */
+ * pool holds up to 2^32 floats (OG_E_NOMEM past that).  Samples stay loaded across og_init.
+ * A sample registered at a rate: OG_E_INVALID before og_init (GraphRateUnset) and on an engine whose rate is not a positive
+ * integer; an equal rate takes the path above; otherwise the source is uploaded once and conformed and channel-mapped on the
+ * device, the sample's length is the conformed one (0 frames: OG_E_INVALID, nothing changes), and the pool limit applies to
+ * the conformed size.  The sample remembers the rate it was conformed to: after an og_init at another rate og_set_sample /
+ * og_set_voice_samples of its index are OG_E_INVALID (SampleRateMismatch).  Samples registered without a rate are never
+ * checked. */
 int og_load_sample(og_engine* e, const char* name, uint32_t* index);
 /* Publishing: the voice plays sample `index` (or OG_SAMPLE_NONE) from its first frame, starting at the first frame of the
  * first block processed after the call returns.  Publishing the index a voice already plays resets its playhead as well

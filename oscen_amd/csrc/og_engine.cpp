@@ -30,6 +30,7 @@
 #include "og_math.h"
 #include "og_registry.h"
 #include "og_bus_conv.hip.h"
+#include "og_asset_resample.hip.h"
 
 // Sum the per-workgroup partial rows (fixed association, no atomics).
 // One workgroup per 16 frames, 64 row-slices x 16 frames = 1024 threads: thread (slice s, frame f) adds
@@ -371,12 +372,22 @@ struct og_graph_desc {
 };
 
 // ---- samples by name (og_register_sample): process-wide, beside the impulse responses --------------------------------
-// interleaved frames as registered, at the graph's rate; a name that exists is replaced (engines that loaded the old
-// one keep their device copy)
+// interleaved frames as registered -- at the graph's rate (og_register_sample: rate 0, untagged) or at their own
+// (og_register_sample_at_rate / og_register_sample_wav: og_load_sample conforms them on the device); a name that exists is
+// replaced (engines that loaded the old one keep their device copy)
 namespace {
 struct SampleData {
     std::vector<float> interleaved;
     uint32_t frames = 0, channels = 1;
+    uint32_t rate = 0; // 0: untagged
+};
+// device memory that lives for one call
+struct DeviceScratch {
+    float* p = nullptr;
+    explicit DeviceScratch(size_t floats) { HIPCK(hipMalloc(&p, std::max<size_t>(floats, 1) * 4)); }
+    ~DeviceScratch() { if (p) (void)hipFree(p); }
+    DeviceScratch(const DeviceScratch&) = delete;
+    DeviceScratch& operator=(const DeviceScratch&) = delete;
 };
 std::map<std::string, std::shared_ptr<const SampleData>>& sample_registry()
 {
@@ -576,8 +587,29 @@ struct og_engine {
     struct LoadedSample {
         std::string name;
         uint32_t frames = 0, channels = 0; // the source's shape (snapshots check it)
+        uint32_t src_rate = 0;             // the source's rate tag (0: untagged, never checked)
+        uint32_t rate = 0;                 // tagged: the graph rate it was conformed to ...
+        uint32_t pool_frames = 0;          // ... and its length in the pool (untagged: `frames`)
         uint32_t off[5] = {0, 0, 0, 0, 0}; // [width]: offset of the width's copy in the pool, in floats
     };
+    // the graph rate a tagged sample is conformed to: og_init's, a positive integer (AudioAsset's rates are u32)
+    uint32_t graph_rate(const char* who) const
+    {
+        if (!inited) throw ogabi::Error(OG_E_INVALID, std::string(who) + ": the graph rate is not set yet (og_init comes first for a sample registered at a rate)");
+        if (!(sr >= 1.0f && sr < 4294967296.0f && sr == floorf(sr)))
+            throw ogabi::Error(OG_E_INVALID, std::string(who) + ": a sample registered at a rate needs an engine rate that is a positive integer, this engine runs at " + std::to_string(sr));
+        return (uint32_t)sr;
+    }
+    // the length a tagged sample has once conformed to `dst` (the checks of from_samples behind the resample)
+    static uint32_t conformed_frames(const std::string& name, const SampleData& sd, uint32_t dst)
+    {
+        if (sd.rate == dst) return sd.frames;
+        const OgResamplePlan p = og_resample_plan(sd.frames, sd.rate, dst);
+        if (p.out_len == 0)
+            throw ogabi::Error(OG_E_INVALID, "sample '" + name + "' (" + std::to_string(sd.frames) + " frames at " + std::to_string(sd.rate) + ") is empty once conformed to " + std::to_string(dst));
+        if (p.out_len >= ((uint64_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
+        return (uint32_t)p.out_len;
+    }
     std::vector<LoadedSample> samples;
     float* d_pool = nullptr;
     size_t pool_used = 0, pool_cap = 0; // floats
@@ -610,7 +642,7 @@ struct og_engine {
         for (size_t k = 0; k < np; ++k)
             for (size_t i = 0; i < samples.size(); ++i) {
                 tab[2 * (k * sample_cap + i)] = samples[i].off[cg->players[k].channels];
-                tab[2 * (k * sample_cap + i) + 1] = samples[i].frames;
+                tab[2 * (k * sample_cap + i) + 1] = samples[i].pool_frames;
             }
         bounce.h2d(d_desc, tab.data(), tab.size() * 4, stream);
         HIPCK(hipStreamSynchronize(stream));
@@ -624,17 +656,35 @@ struct og_engine {
         ls.name = name;
         ls.frames = sd.frames;
         ls.channels = sd.channels;
+        ls.src_rate = sd.rate;
+        ls.rate = sd.rate ? graph_rate("og_load_sample") : 0u;
+        ls.pool_frames = sd.rate ? conformed_frames(name, sd, ls.rate) : sd.frames;
+        const bool conform = sd.rate && sd.rate != ls.rate; // (an equal rate takes the untagged path)
         bool widths[5] = {false, false, false, false, false};
         size_t need = pool_used;
         for (const auto& pl : cg->players)
             if (!widths[pl.channels]) {
                 widths[pl.channels] = true;
-                need += (size_t)sd.frames * pl.channels;
+                need += (size_t)ls.pool_frames * pl.channels;
             }
         if (need >= ((size_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
         pool_reserve(need);
+        if (conform) { // the source goes up once; conformed and mapped on the device, straight into the pool
+            const OgResamplePlan plan = og_resample_plan(sd.frames, sd.rate, ls.rate);
+            DeviceScratch d_src(sd.interleaved.size()), d_conf((size_t)ls.pool_frames * sd.channels);
+            bounce.h2d(d_src.p, sd.interleaved.data(), sd.interleaved.size() * 4, stream);
+            og_resample_launch(d_src.p, sd.frames, sd.channels, plan, d_conf.p, stream);
+            for (uint32_t w = 1; w <= 4; ++w) {
+                if (!widths[w]) continue;
+                ls.off[w] = (uint32_t)pool_used;
+                og_map_channels_launch(d_conf.p, ls.pool_frames, sd.channels, w, d_pool + pool_used, stream);
+                pool_used += (size_t)ls.pool_frames * w;
+            }
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(stream));
+        }
         std::vector<float> mapped;
-        for (uint32_t w = 1; w <= 4; ++w) {
+        for (uint32_t w = 1; w <= 4 && !conform; ++w) {
             if (!widths[w]) continue;
             ls.off[w] = (uint32_t)pool_used;
             mapped.resize((size_t)sd.frames * w);
@@ -2593,21 +2643,108 @@ int og_set_voice_value(og_engine* e, uint32_t input, uint32_t voice, float v)
 }
 
 // ---- SamplePlayer: registry, device pool, publishing ------------------------------------------------------------------
-int og_register_sample(const char* name, const float* interleaved, uint64_t frames, uint32_t channels)
+namespace {
+// rate 0: untagged (og_register_sample)
+int register_sample(const char* who, const char* name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t rate)
 {
-    return ogabi::guard([&]() -> int {
-    if (!name || !*name) return set_err(OG_E_INVALID, "og_register_sample: a sample needs a name");
+    if (!name || !*name) return set_err(OG_E_INVALID, std::string(who) + ": a sample needs a name");
     if (channels < 1 || channels > OG_MAX_SAMPLE_CHANNELS)
-        return set_err(OG_E_INVALID, "og_register_sample: 1 to " + std::to_string(OG_MAX_SAMPLE_CHANNELS) + " channels");
+        return set_err(OG_E_INVALID, std::string(who) + ": 1 to " + std::to_string(OG_MAX_SAMPLE_CHANNELS) + " channels");
     if (frames > OG_MAX_SAMPLE_FLOATS / channels)
-        return set_err(OG_E_INVALID, "og_register_sample: '" + std::string(name) + "' has more than 2^28 samples (frames x channels)");
+        return set_err(OG_E_INVALID, std::string(who) + ": '" + std::string(name) + "' has more than 2^28 samples (frames x channels)");
     if (frames && !interleaved) return set_err(OG_E_INVALID, "null argument");
     auto sd = std::make_shared<SampleData>();
     sd->frames = (uint32_t)frames;
     sd->channels = channels;
+    sd->rate = rate;
     if (frames) sd->interleaved.assign(interleaved, interleaved + (size_t)frames * channels);
     std::lock_guard<std::mutex> lk(sample_registry_lock());
     sample_registry()[name] = sd;
+    return OG_OK;
+}
+// host buffers through the resample kernel on the current device (og_resample)
+void resample_on_device(const float* in, uint64_t frames, uint32_t channels, const OgResamplePlan& plan, float* out)
+{
+    DeviceScratch d_src((size_t)frames * channels), d_dst((size_t)plan.out_len * channels);
+    HIPCK(hipMemcpy(d_src.p, in, (size_t)frames * channels * 4, hipMemcpyHostToDevice));
+    og_resample_launch(d_src.p, frames, channels, plan, d_dst.p, nullptr);
+    HIPCK(hipGetLastError());
+    HIPCK(hipDeviceSynchronize());
+    HIPCK(hipMemcpy(out, d_dst.p, (size_t)plan.out_len * channels * 4, hipMemcpyDeviceToHost));
+}
+} // namespace
+
+int og_register_sample(const char* name, const float* interleaved, uint64_t frames, uint32_t channels)
+{
+    return ogabi::guard([&]() -> int { return register_sample("og_register_sample", name, interleaved, frames, channels, 0u); });
+}
+
+// AudioAsset::from_samples' own checks (asset/mod.rs:175-192): an empty asset and a zero rate are refused
+int og_register_sample_at_rate(const char* name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t sample_rate)
+{
+    return ogabi::guard([&]() -> int {
+    if (sample_rate == 0) return set_err(OG_E_INVALID, "og_register_sample_at_rate: the sample rate is 0");
+    if (frames == 0) return set_err(OG_E_INVALID, "og_register_sample_at_rate: the sample is empty");
+    return register_sample("og_register_sample_at_rate", name, interleaved, frames, channels, sample_rate);
+    });
+}
+
+int og_sample_info(const char* name, uint64_t* frames, uint32_t* channels, uint32_t* sample_rate)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name) return set_err(OG_E_INVALID, "null argument");
+    const auto sd = lookup_sample(name);
+    if (!sd) return set_err(OG_E_INVALID, std::string("no sample '") + name + "'");
+    if (frames) *frames = sd->frames;
+    if (channels) *channels = sd->channels;
+    if (sample_rate) *sample_rate = sd->rate;
+    return OG_OK;
+    });
+}
+
+int og_read_sample(const char* name, float* out, uint64_t capacity_frames)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name || !out) return set_err(OG_E_INVALID, "null argument");
+    const auto sd = lookup_sample(name);
+    if (!sd) return set_err(OG_E_INVALID, std::string("no sample '") + name + "'");
+    if (capacity_frames < sd->frames) return set_err(OG_E_INVALID, "og_read_sample: the output holds " + std::to_string(capacity_frames) + " frames, the sample has " + std::to_string(sd->frames));
+    if (!sd->interleaved.empty()) memcpy(out, sd->interleaved.data(), sd->interleaved.size() * 4);
+    return OG_OK;
+    });
+}
+
+int og_resample_frames(uint64_t frames, uint32_t src_rate, uint32_t dst_rate, uint64_t* out_frames)
+{
+    return ogabi::guard([&]() -> int {
+    if (!out_frames) return set_err(OG_E_INVALID, "null argument");
+    if (src_rate == 0 || dst_rate == 0) return set_err(OG_E_INVALID, "og_resample_frames: the sample rate is 0");
+    if (frames > OG_MAX_SAMPLE_FLOATS) return set_err(OG_E_INVALID, "og_resample_frames: more than 2^28 frames");
+    *out_frames = frames == 0 || src_rate == dst_rate ? frames : og_resample_plan(frames, src_rate, dst_rate).out_len;
+    return OG_OK;
+    });
+}
+
+int og_resample(const float* interleaved, uint64_t frames, uint32_t channels, uint32_t src_rate, uint32_t dst_rate, float* out,
+                uint64_t out_capacity_frames)
+{
+    return ogabi::guard([&]() -> int {
+    if (!interleaved || !out) return set_err(OG_E_INVALID, "null argument");
+    if (src_rate == 0 || dst_rate == 0) return set_err(OG_E_INVALID, "og_resample: the sample rate is 0");
+    if (frames == 0) return set_err(OG_E_INVALID, "og_resample: the input is empty");
+    if (channels < 1 || channels > OG_MAX_SAMPLE_CHANNELS)
+        return set_err(OG_E_INVALID, "og_resample: 1 to " + std::to_string(OG_MAX_SAMPLE_CHANNELS) + " channels");
+    if (frames > OG_MAX_SAMPLE_FLOATS / channels) return set_err(OG_E_INVALID, "og_resample: more than 2^28 samples (frames x channels)");
+    const OgResamplePlan plan = og_resample_plan(frames, src_rate, dst_rate);
+    const uint64_t n = src_rate == dst_rate ? frames : plan.out_len;
+    if (n > out_capacity_frames)
+        return set_err(OG_E_INVALID, "og_resample: the output holds " + std::to_string(out_capacity_frames) + " frames, " + std::to_string(n) + " are needed (og_resample_frames)");
+    if (n > OG_MAX_SAMPLE_FLOATS / channels) return set_err(OG_E_INVALID, "og_resample: the output has more than 2^28 samples (frames x channels)");
+    if (src_rate == dst_rate) {
+        memmove(out, interleaved, (size_t)frames * channels * 4);
+        return OG_OK;
+    }
+    if (n) resample_on_device(interleaved, frames, channels, plan, out);
     return OG_OK;
     });
 }
@@ -2649,6 +2786,12 @@ int og_set_voice_samples(og_engine* e, const char* node, uint32_t first, uint32_
         for (uint32_t i = 0; i < count; ++i)
             if (indices[i] != OG_SAMPLE_NONE && indices[i] >= e->samples.size())
                 return set_err(OG_E_INVALID, "sample index " + std::to_string(indices[i]) + " was not handed out by og_load_sample");
+        for (uint32_t i = 0; i < count; ++i) { // SampleRateMismatch: a conformed sample plays at the rate it was conformed to only
+            if (indices[i] == OG_SAMPLE_NONE) continue;
+            const auto& ls = e->samples[indices[i]];
+            if (ls.src_rate && (float)ls.rate != e->sr)
+                return set_err(OG_E_INVALID, "sample '" + ls.name + "' was conformed to " + std::to_string(ls.rate) + " Hz, the engine now runs at " + std::to_string(e->sr) + " Hz");
+        }
         if (!count) return OG_OK;
         HIPCK(hipSetDevice(e->device));
         e->flush_bus(); // queued blocks keep what they were queued under: the words are written behind them, in stream order
@@ -3442,11 +3585,24 @@ struct SnapSample {
     uint32_t name_len, frames, channels, reserved;
 };
 constexpr uint32_t SNAP_SMP_MAGIC = 0x504D534Fu; // "OSMP"
+// ... and, ONLY when a sample registered at a rate is loaded (a blob without one stays what it was), the section has another
+// magic and every entry is followed by the rates: og_load_state conforms again from the registry and compares
+struct SnapSampleRate {
+    uint32_t src_rate, rate, pool_frames, reserved; // src_rate 0: an untagged sample among tagged ones
+};
+constexpr uint32_t SNAP_SMPR_MAGIC = 0x524D534Fu; // "OSMR"
+bool samples_tagged(const og_engine* e)
+{
+    for (const auto& ls : e->samples)
+        if (ls.src_rate) return true;
+    return false;
+}
 size_t samples_bytes(const og_engine* e)
 {
     if (e->cg->players.empty()) return 0;
     size_t n = sizeof(SnapSamples);
-    for (const auto& ls : e->samples) n += sizeof(SnapSample) + (ls.name.size() + 3) / 4 * 4;
+    const size_t extra = samples_tagged(e) ? sizeof(SnapSampleRate) : 0;
+    for (const auto& ls : e->samples) n += sizeof(SnapSample) + (ls.name.size() + 3) / 4 * 4 + extra;
     return n;
 }
 
@@ -3546,7 +3702,8 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
             p += hf * vc * 4;
         }
         if (!e->cg->players.empty()) {
-            const SnapSamples sh{SNAP_SMP_MAGIC, (uint32_t)e->samples.size()};
+            const bool tagged = samples_tagged(e);
+            const SnapSamples sh{tagged ? SNAP_SMPR_MAGIC : SNAP_SMP_MAGIC, (uint32_t)e->samples.size()};
             memcpy(p, &sh, sizeof sh);
             p += sizeof sh;
             for (const auto& ls : e->samples) {
@@ -3557,6 +3714,11 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
                 memset(p, 0, padded);
                 memcpy(p, ls.name.data(), ls.name.size());
                 p += padded;
+                if (tagged) {
+                    const SnapSampleRate sr{ls.src_rate, ls.rate, ls.pool_frames, 0u};
+                    memcpy(p, &sr, sizeof sr);
+                    p += sizeof sr;
+                }
             }
         }
         return OG_OK;
@@ -3583,6 +3745,7 @@ int og_load_state(og_engine* e, const void* src, size_t len)
     struct WantSample {
         std::string name;
         uint32_t frames, channels;
+        uint32_t src_rate, rate, pool_frames;
     };
     std::vector<WantSample> want_samples;
     if (!e->cg->players.empty()) {
@@ -3601,7 +3764,8 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             SnapSamples sh{};
             bool ok = full_len - at >= sizeof sh;
             if (ok) memcpy(&sh, (const char*)src + at, sizeof sh);
-            ok = ok && sh.magic == SNAP_SMP_MAGIC;
+            const bool tagged = ok && sh.magic == SNAP_SMPR_MAGIC;
+            ok = ok && (sh.magic == SNAP_SMP_MAGIC || tagged);
             at += sizeof sh;
             for (uint32_t i = 0; ok && i < sh.n; ++i) {
                 SnapSample ss{};
@@ -3612,8 +3776,18 @@ int og_load_state(og_engine* e, const void* src, size_t len)
                 const size_t padded = ((size_t)ss.name_len + 3) / 4 * 4;
                 ok = ss.name_len <= 4096u && full_len - at >= padded;
                 if (!ok) break;
-                want_samples.push_back({std::string((const char*)src + at, ss.name_len), ss.frames, ss.channels});
+                want_samples.push_back({std::string((const char*)src + at, ss.name_len), ss.frames, ss.channels, 0u, 0u, ss.frames});
                 at += padded;
+                if (tagged) {
+                    SnapSampleRate sr{};
+                    ok = full_len - at >= sizeof sr;
+                    if (!ok) break;
+                    memcpy(&sr, (const char*)src + at, sizeof sr);
+                    at += sizeof sr;
+                    want_samples.back().src_rate = sr.src_rate;
+                    want_samples.back().rate = sr.rate;
+                    want_samples.back().pool_frames = sr.pool_frames;
+                }
             }
             if (!ok || at != full_len) return set_err(OG_E_INVALID, "state blob: the SamplePlayer section is missing or malformed");
             // every sample must be there, in the shape it was saved with, before anything is changed
@@ -3621,7 +3795,8 @@ int og_load_state(og_engine* e, const void* src, size_t len)
                 const WantSample& w = want_samples[i];
                 if (i < e->samples.size()) {
                     const auto& ls = e->samples[i];
-                    if (ls.name != w.name || ls.frames != w.frames || ls.channels != w.channels)
+                    if (ls.name != w.name || ls.frames != w.frames || ls.channels != w.channels || ls.src_rate != w.src_rate ||
+                        ls.pool_frames != w.pool_frames)
                         return set_err(OG_E_INVALID, "state blob: sample " + std::to_string(i) + " is '" + w.name + "', this engine has loaded '" + ls.name + "' there");
                     continue;
                 }
@@ -3629,6 +3804,11 @@ int og_load_state(og_engine* e, const void* src, size_t len)
                 if (!sd) return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is not registered (og_register_sample)");
                 if (sd->frames != w.frames || sd->channels != w.channels)
                     return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is registered with another shape than the one it was saved with");
+                if (sd->rate != w.src_rate)
+                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' was saved at source rate " + std::to_string(w.src_rate) + ", it is registered at " + std::to_string(sd->rate) + " (0: no rate)");
+                if (sd->rate && (e->graph_rate("og_load_state") != w.rate ||
+                                 og_engine::conformed_frames(w.name, *sd, w.rate) != w.pool_frames))
+                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' was saved with " + std::to_string(w.pool_frames) + " frames conformed to " + std::to_string(w.rate) + " Hz; this engine's rate or the registered data give another length");
             }
             full_len = smp_at;
             return OG_OK;
@@ -3690,7 +3870,7 @@ int og_load_state(og_engine* e, const void* src, size_t len)
         HIPCK(hipStreamSynchronize(e->stream));
         for (size_t i = e->samples.size(); i < want_samples.size(); ++i) { // (validated above; the registry may have changed since)
             const auto sd = lookup_sample(want_samples[i].name);
-            if (!sd || sd->frames != want_samples[i].frames || sd->channels != want_samples[i].channels)
+            if (!sd || sd->frames != want_samples[i].frames || sd->channels != want_samples[i].channels || sd->rate != want_samples[i].src_rate)
                 throw ogabi::Error(OG_E_INVALID, "state blob: sample '" + want_samples[i].name + "' is not registered in the shape it was saved with");
             (void)e->load_sample(want_samples[i].name, *sd);
         }
