@@ -456,6 +456,7 @@ struct og_engine {
     // the deeper zero variant (og_graph.cpp, ZeroFolds): tier 2 of the registry
     OgZeroLaunchFn launch_zero2 = nullptr;
     bool zero2_spec = true; // launches may run it (OSCEN_GPU_ZERO2_SPEC=0, or OSCEN_GPU_ZERO_SPEC=0: never)
+    bool stage_spec = true; // ... with its stage-uniform envelope bodies (OSCEN_GPU_STAGE_SPEC=0: the general quiet bodies only)
     bool guards_held = true; // every launch so far had finite values in cg->finite_slots: no operator state can hold inf / NaN
     int last_tier = 0;       // what the last launch ran: 0 general, 1 zero variant, 2 deeper zero variant (og_kernel_fold_tier)
     std::unique_ptr<OgJitKernel> jit;
@@ -1774,6 +1775,9 @@ struct og_engine {
         for (int zs : cg->zero2_slots) zero2 = zero2 && (A.slots[zs] & 0x7fffffffu) == 0u;
         last_zero = false;
         last_tier = 0;
+        // (OSCEN_GPU_STAGE_SPEC=0: the deeper variant without its stage-uniform envelope bodies -- the switch is the last uniform
+        //  slot, which a graph that has the bodies does not use, og_stage_uniform.hip.h; the other kernels never read it)
+        if (zero2 && !stage_spec && cg->stage_spec) A.slots[OG_MAX_SLOTS - 1] = 1u;
         if (zero2 && (launch ? launch_zero2 != nullptr : jit->launch_zero2(A, taps_on, stream))) {
             if (launch) launch_zero2(A, taps_on, stream);
             last_zero = true;
@@ -2341,6 +2345,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             e->blocking_memcpy = ogabi::experiment_knob("OSCEN_GPU_BLOCKING_MEMCPY") != nullptr; // (environment knobs are read HERE, once)
             if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO_SPEC")) e->zero_spec = atoi(zs) != 0;
             if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO2_SPEC")) e->zero2_spec = atoi(zs) != 0;
+            if (const char* ss = ogabi::experiment_knob("OSCEN_GPU_STAGE_SPEC")) e->stage_spec = atoi(ss) != 0;
             if (const char* rc = ogabi::experiment_knob("OSCEN_GPU_RCP_CAP")) e->rcp_cap = std::min<uint32_t>(OG_RCP_MAX, (uint32_t)atoll(rc));
             if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) e->ev_headroom_env = std::max<size_t>(64, (size_t)atoll(hv));
             uint32_t lanes = OG_WAVE;

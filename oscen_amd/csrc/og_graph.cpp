@@ -515,6 +515,8 @@ struct Codegen {
     // well.  What the general pass learned for finding them: the slot of every FmOperator's block-uniform feedback and level
     // (-1: neither a slot nor, for the level, a finite literal; -2: a finite literal level) and of every Crossfade's mix
     std::map<int, int> fm_fb_slot, fm_level_slot, xfade_mix_slot;
+    // ... and its four-wave pipeline gets the stage-uniform envelope bodies (PipelineWave::fast_variants, og_stage_uniform.hip.h)
+    bool stage_spec = false;
     // pipeline bookkeeping
     bool split = false;
     int n_stages = 1;
@@ -4632,6 +4634,7 @@ struct PipelineWave {
     std::set<int> producers, consumers;
     std::string wait_all, taken, sync_line;
     bool tab_ok = false;
+    bool stage_bodies = false; // this wave has the hold and the pure-release body (the deeper zero variant, four waves, envelopes)
     const char* force = nullptr;
     int rel_prio = -1;
 
@@ -4644,9 +4647,10 @@ struct PipelineWave {
     void chunk_loop();
     void epilogue();
     std::string call(const std::string& flag) const;
+    std::string call_as(const std::string& chk) const;
     std::string bus_tail(const std::string& ind, const std::string& n_expr) const;
     std::string row_fetch(const std::string& ind) const;
-    void quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string());
+    void quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string(), int env_mode = 0);
     void checked(const std::string& ind);
     void variants(bool st_flag, const std::string& ind0);
     void fast_variants(bool st_flag, const std::string& ind0);
@@ -4811,9 +4815,13 @@ void PipelineWave::prologue()
         }
     }
     for (int r : rows) body << "    float rv_" << r << "[XCH];\n";
+    // (the stage-uniform bodies: the same tick site, the chunk flag says which envelope arithmetic it runs)
+    stage_bodies = cg.stage_spec && K == 4 && !envs.empty() && !cg.uses_adsrp;
     for (const auto& E : envs) {
         const std::string from = "og::adsr_tick<decltype(chk)::release, true>(" + E + ")";
-        const std::string to = "og::adsr_tick_chunk<decltype(chk)::release, decltype(chk)::table>(" + E + ", " + E + "_rcp, j)";
+        const std::string to = (stage_bodies ? "og::adsr_tick_stage<og::env_mode(decltype(chk){}), decltype(chk)::release, decltype(chk)::table>("
+                                             : "og::adsr_tick_chunk<decltype(chk)::release, decltype(chk)::table>(") +
+                               E + ", " + E + "_rcp, j)";
         const size_t pos = tick_text.find(from);
         if (pos == std::string::npos) throw std::runtime_error("internal: no tick of " + E + " in its wave");
         tick_text.replace(pos, from.size(), to);
@@ -4828,9 +4836,11 @@ void PipelineWave::prologue()
 
 // SALU instructions cost issue slots like VALU ones: the quiet chunk is a straight-line,
 // fully unrolled body; per-frame tests only exist on the (rare) event path
-std::string PipelineWave::call(const std::string& flag) const
+std::string PipelineWave::call(const std::string& flag) const { return call_as("og::BoolC<" + flag + ">"); }
+
+std::string PipelineWave::call_as(const std::string& chk) const
 {
-    const std::string t = std::string("tick(f, ch, j, og::BoolC<") + flag + ">{})";
+    const std::string t = "tick(f, ch, j, " + chk + "{})";
     // row of the bus tile: f % OG_BUS_CHUNK = (base % OG_BUS_CHUNK) + j -- `base` is a multiple of XCH, which divides
     // OG_BUS_CHUNK, so there is no carry; written this way the chunk-invariant part is formed once per chunk and the
     // eight stores of the unrolled body take immediate offsets (one v_add + two SALU per frame less in the bus wave)
@@ -4916,7 +4926,9 @@ std::string PipelineWave::row_fetch(const std::string& ind) const
 // (FD_T != 0; the 8-frame one keeps v_rcp_f32): one 16-byte load per envelope and four frames.  A wide launch whose
 // releases the table does not cover (rcp_len = 0) sends chunks with a releasing lane to the checked body instead
 // (`rel_ok` in the quiet test below).  Only where the checked body is the alternative (one_checked).
-void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay)
+// env_mode 1 / 2: the hold / the pure-release body of the stage-uniform envelopes -- the release-free / the release loop with
+// another chunk flag (og::StageC) and nothing else changed.
+void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay, int env_mode)
 {
     const bool pre = !reads.empty() || !rows.empty();
     const bool loop = sticky && !stay.empty();
@@ -4943,10 +4955,13 @@ void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_fla
     }
     const std::string flag = std::string(chk_flag) + ", " + rel_flag + ", " + (pre ? "true" : "false") + ", " +
                              (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "");
+    const std::string stage_flag = std::string("og::StageC<") + (env_mode == 1 ? "og::ENV_HOLD" : "og::ENV_RELEASE") + ", " + (pre ? "true" : "false") + ", " +
+                                   (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "") + ">";
+    if (env_mode) body << ind << "og::stage_body_count<" << (env_mode == 1 ? "og::ENV_HOLD" : "og::ENV_RELEASE") << ">(" << gi << "u);\n";
     body << ind << "#pragma unroll\n"
          << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
          << ind << "    const uint32_t f = base + j;\n"
-         << ind << "    " << call(flag) << "\n";
+         << ind << "    " << (env_mode ? call_as(stage_flag) : call(flag)) << "\n";
     // (the next chunk's four reciprocals go into the registers these frames have just read: nothing moves across the
     //  back edge; a chunk the loop then leaves has loaded them for nothing, inside the table's padding)
     if (tab) {
@@ -4954,6 +4969,10 @@ void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_fla
         for (const auto& E : envs) body << ind << "        og::rcp_refill<XCH>(" << E << "_rcp, A, " << E << "_nx, j);\n";
         body << ind << "    }\n";
     }
+    // (a stage with several envelopes: the pure-release ticks are one fma each, and left alone the scheduler runs every
+    //  envelope's chain for the whole chunk ahead of the operator -- fm_voice's og_k4w_*_00z2 then takes 124 VGPRs, a granule
+    //  more than its `_z` twin; fenced in the middle of the chunk it takes 118)
+    if (env_mode == 2 && envs.size() > 1) body << ind << "    og::stage_sched_fence<XCH>(j);\n";
     body << ind << "}\n";
     if (loop) {
         body << ind << "const uint32_t ch1 = ch + 1u, base1 = base + XCH;\n"
@@ -5011,13 +5030,39 @@ void PipelineWave::variants(bool st_flag, const std::string& ind0)
 void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
 {
     const std::string no_rel = "__all((int)(" + bw.rs_sum(st) + " == 0.0f))";
+    // Stage-uniform envelope bodies (og_stage_uniform.hip.h has the rules and their proofs): next to each of the two loops a
+    // second one for the chunks in which EVERY envelope of the stage, in every lane, holds / releases.  What the entry tests
+    // reads -- rs, cf, tgt, and in the hold body lv -- does not change inside a quiet loop, so each body keeps its neighbour's stay
+    // condition; a wave changes body only through the chunk loop's head, after the event or the stage end that changed them.
+    std::string holds, releases;
+    for (const auto& E : envs) {
+        holds += (holds.empty() ? "" : " && ") + ("og::adsr_holds(" + E + ")");
+        releases += (releases.empty() ? "" : " && ") + ("og::adsr_releases(" + E + ")");
+    }
+    const bool bodies = stage_bodies && tab_ok && sticky;
     body << ind0 << "if (" << no_rel << ") { // no lane is in Release\n";
-    quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "    ", no_rel);
+    if (bodies) {
+        body << ind0 << "    if (og::stage_spec_on(A) && __all((int)(" << holds << "))) { // ... and every envelope holds its level\n";
+        quiet("false", "false", st_flag, ind0 + "        ", no_rel, 1);
+        body << ind0 << "    } else {\n";
+        quiet("false", "false", st_flag, ind0 + "        ", no_rel);
+        body << ind0 << "    }\n";
+    } else {
+        quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "    ", no_rel);
+    }
     body << ind0 << "} else {\n";
     // OGC_RELPRIO=n (experiment for grouped banks, og_group_voices: the waves that release are then few and
     // whole, and their workgroups are the ones a launch waits for; measured WITHOUT grouping in round 4: loses)
     if (rel_prio >= 0) body << ind0 << "    __builtin_amdgcn_s_setprio(" << rel_prio << ");\n";
-    quiet("false", "true", st_flag, ind0 + "    ", "!" + no_rel);
+    if (bodies) {
+        body << ind0 << "    if (og::stage_spec_on(A) && __all((int)(!c.valid || (" << releases << ")))) { // every envelope of every voice releases\n";
+        quiet("false", "true", st_flag, ind0 + "        ", "!" + no_rel, 2);
+        body << ind0 << "    } else {\n";
+        quiet("false", "true", st_flag, ind0 + "        ", "!" + no_rel);
+        body << ind0 << "    }\n";
+    } else {
+        quiet("false", "true", st_flag, ind0 + "    ", "!" + no_rel);
+    }
     if (rel_prio >= 0) body << ind0 << "    og::set_prio<BASE_PRIO>();\n";
     body << ind0 << "}\n";
 }
@@ -5186,13 +5231,14 @@ struct Lowered {
 //   form_graph_output         out_edges, out_reads, ev_out_edges, the bus ends  -> bus_expr, out.output_channels / event_outputs / channels
 //   choose_unroll             order, out.rings / players / lpv                  -> unroll, out.valu_estimate
 //   BodyWriter                cg.sec[], cg.xvals, the groups, bus_expr, unroll  -> body
-std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_nodes)
+std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_nodes, bool stage_spec = false)
 {
     check_reference_rules(g_in);
     auto gen = std::make_unique<Lowered>(g_in);
     gen->out->name = gen->g.name;
     Codegen& cg = gen->cg;
     cg.zero_nodes = zero_nodes;
+    cg.stage_spec = stage_spec;
     Lowering& lw = gen->lw;
     lw.declare_inputs_outputs();
     lw.declare_nodes();
@@ -5218,11 +5264,11 @@ std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_
 // A zero variant's pass: the kernel body with `nodes` folded, or "" where the graph does not get that variant.  The engine
 // fills the slots and the state of every kernel from the general pass's layout: a variant pass that does not keep it (or does
 // not compile) leaves the graph without the variant -- it never costs the graph its general kernel.
-std::string lower_variant(const GraphDesc& g_in, const std::set<int>& nodes, const CompiledGraph& out)
+std::string lower_variant(const GraphDesc& g_in, const std::set<int>& nodes, const CompiledGraph& out, bool stage_spec = false)
 {
     if (nodes.empty()) return std::string();
     try {
-        const auto zgen = lower(g_in, &nodes);
+        const auto zgen = lower(g_in, &nodes, stage_spec);
         const CompiledGraph& z = *zgen->out;
         bool same = z.n_slots == out.n_slots && z.state.size() == out.state.size() && z.n_ramps == out.n_ramps && z.n_streams == out.n_streams &&
                     z.lpv == out.lpv && z.max_pipeline == out.max_pipeline && z.wide4 == out.wide4;
@@ -5429,10 +5475,15 @@ ZeroFolds find_zero_folds(Lowered& gen)
 // ---- the translation units: the general kernels' (csrc/gen/<graph>.hip) and the zero variants' (<graph>_z.hip, _z2.hip) ------
 // a unit from its first line to the end of its namespace; `desc` is what its head comment says after the GENERATED line
 void write_unit_head(std::ostringstream& os, const std::string& graph, const std::string& desc, const std::string& pre, const std::string& ns, int lpv,
-                     const std::string& body)
+                     const std::string& body, const std::string& more_includes = std::string())
 {
+    std::string pre_inc = pre;
+    if (!more_includes.empty()) { // behind the last of the common includes
+        const size_t at = pre_inc.find("\n\n#if OG_NODE_EVENTS_PER_FRAME");
+        pre_inc.insert(at == std::string::npos ? pre_inc.size() : at + 1, more_includes);
+    }
     os << "// GENERATED by oscen_amd/csrc/og_graph.cpp from graph '" << graph << "' -- do not edit.\n"
-       << desc << pre << "namespace " << ns << " {\nconstexpr int LPV = " << lpv << "; // lanes per voice\n"
+       << desc << pre_inc << "namespace " << ns << " {\nconstexpr int LPV = " << lpv << "; // lanes per voice\n"
        << body << "} // namespace\n\n"
        << "#undef SF\n#undef SU\n#undef RV\n#undef ST\n#undef RVP\n#undef STP\n\n";
 }
@@ -5517,6 +5568,9 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     for (const NodeInst& n : cg.nodes)
         if (zset.count(n.id) || z2set.count(n.id)) z2desc << " " << n.decl->name;
     z2desc << ".";
+    if (out.stage_spec)
+        z2desc << "\n// Its four-wave pipeline has the stage-uniform envelope bodies of og_stage_uniform.hip.h (digest " << OG_STAGEU_DIGEST
+               << "); uniform slot 159 switches them off.";
     // (the preamble of a unit: the zero variant's unit has the same one)
     std::ostringstream pre;
     if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
@@ -5533,7 +5587,9 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     const std::string ns = std::string("og_gen_") + hs;
     write_unit_head(units[0].os, g.name, desc.str(), pre.str(), ns, out.lpv, gen.body);
     if (units[1].on) write_unit_head(units[1].os, g.name, zdesc.str(), pre.str(), ns + "_z", out.lpv, zbody);
-    if (units[2].on) write_unit_head(units[2].os, g.name, z2desc.str(), pre.str(), ns + "_z2", out.lpv, z2body);
+    if (units[2].on)
+        write_unit_head(units[2].os, g.name, z2desc.str(), pre.str(), ns + "_z2", out.lpv, z2body,
+                        out.stage_spec ? "#include \"og_stage_uniform.hip.h\"\n" : "");
 
     const char* variants[4][3] = {{"00", "false", "false"}, {"10", "true", "false"}, {"01", "false", "true"},
                                   {"11", "true", "true"}};
@@ -5639,7 +5695,12 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     ZeroFolds z2 = find_zero_folds(*gen);
     std::set<int> all = zset;
     all.insert(z2.nodes.begin(), z2.nodes.end());
-    const std::string z2body = lower_variant(g_in, z2.nodes.empty() ? z2.nodes : all, out);
+    // (stage-uniform envelope bodies in its four-wave pipeline: OGC_STAGE_SPEC=0 writes the unit without them; the last uniform
+    //  slot must be free -- it carries the engine's A/B switch, OG_STAGE_SPEC_SLOT)
+    const char* ssk = ogabi::experiment_knob("OGC_STAGE_SPEC");
+    out.stage_spec = !(ssk && atoi(ssk) == 0) && out.n_slots < 160;
+    std::string z2body = lower_variant(g_in, z2.nodes.empty() ? z2.nodes : all, out, out.stage_spec);
+    out.stage_spec = out.stage_spec && z2body.find("og::StageC<") != std::string::npos;
     if (z2body.empty()) {
         z2.nodes.clear();
     } else {

@@ -166,6 +166,7 @@ struct CompiledGraph {
     // the deeper zero variant (og_graph.cpp, ZeroFolds): a launch runs og_k*_<hash>_{00,01}z2 when every slot of zero2_slots
     // (zero_slots included) holds +-0 and every slot of finite_slots holds a finite value (empty zero2_slots: no such kernel)
     std::vector<int> zero2_slots, finite_slots;
+    bool stage_spec = false; // ... and its four-wave pipeline has the stage-uniform envelope bodies (og_stage_uniform.hip.h)
     int valu_estimate = 0;             // estimated VALU instructions per frame of one wave of the ordinary kernel (node weights)
     // post-mix stage: one node on the summed bus.  Tremolo (electric-piano/src/main.rs:88-96) -> Frame<2>; Convolver
     // (oscen-lib/src/convolution/mod.rs) -> as many channels as the voices
