@@ -1,5 +1,4 @@
-// og_cluster.inl -- multi-GPU voice banks behind the C ABI (textually included at the end of og_engine.cpp:
-// it works on og_engine's internals).
+// og_cluster.cpp -- multi-GPU voice banks behind the C ABI (it works on og_engine's internals: og_engine.h).
 //
 // SURVEY 8(e) / examples/fm-synth/src/lib.rs:269-274: voices are independent, the only cross-voice operation is
 // the sum onto the mix bus.  A cluster owns one engine ("shard") per entry of device_ids; shard s holds the
@@ -14,6 +13,8 @@
 //
 // RCCL is bound at run time (dlopen) the first time a cluster spans more than one device: a single-GPU user of
 // liboscen_gpu.so does not need it.
+#include "og_engine.h"
+
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
@@ -358,8 +359,7 @@ struct og_cluster {
             const float rate = e0->cg->tremolo_rate(env), depth = e0->cg->tremolo_depth(env);
             for (size_t g = 0; g < nf; g += OG_MAX_BLOCK) {
                 const uint32_t frames = (uint32_t)std::min<size_t>(OG_MAX_BLOCK, nf - g);
-                hipLaunchKernelGGL(og_bus_tremolo, dim3(1), dim3(512), 0, dev_stream[0], mono + g, frames, rate, depth, e0->sr,
-                                   d_phase, d_out + 2 * g);
+                og_engine::launch_bus_tremolo(mono + g, frames, rate, depth, e0->sr, d_phase, d_out + 2 * g, dev_stream[0]);
             }
             HIPCK(hipMemcpyAsync(h_pin[b], d_out, nf * 2 * sizeof(float), hipMemcpyDeviceToHost, dev_stream[0]));
         } else {
@@ -479,8 +479,8 @@ int og_cluster_create(const og_graph_desc* g, uint64_t n_voices_total, const int
             og_engine* raw = nullptr;
             const int rc = og_create(g, (uint32_t)nv, device_ids[s], &raw);
             if (rc != OG_OK) {
-                if (rc == OG_E_DEVICE) throw HipError(g_err);
-                throw std::runtime_error(g_err);
+                if (rc == OG_E_DEVICE) throw HipError(og_last_error());
+                throw std::runtime_error(og_last_error());
             }
             std::unique_ptr<og_engine> e(raw); // (owned here until the cluster has it: alloc_bus_buffers may throw)
             if (e->cg->bus_stage == ogc::BusStage::Convolver) // (the stage would run once on the root, after the reduce: not built)

@@ -6,29 +6,8 @@
 // (examples/fm-synth/src/lib.rs:22-131): `voices = [Voice; N]`, every broadcast
 // value input fanned out to all voices (ramped where declared `[ramp: N]`),
 // per-voice `frequency`/`gate`, and `voices.out -> out` summed onto the bus.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <deque>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <stdexcept>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/oscen_gpu.h"
-#include "og_abi.h"
-#include "og_graph.h"
-#include "og_jit.h"
+#include "og_engine.h"
 #include "og_math.h"
-#include "og_registry.h"
 #include "og_bus_conv.hip.h"
 #include "og_asset_resample.hip.h"
 
@@ -140,7 +119,6 @@ __global__ __launch_bounds__(512) void og_bus_tremolo(const float* __restrict__ 
 // whereas hipMemcpyAsync of a small pinned buffer was measured to block until the stream had drained (~290 us with a
 // batch of blocks in flight), which serialised the host's event preparation with the GPU.
 // upd = n x {voice, cursor, end}
-constexpr size_t EV_UPD_WORDS = 3;
 __global__ void og_apply_event_updates(const uint4* __restrict__ staged, uint32_t n_ev, uint4* __restrict__ timeline_tail,
                                        const uint32_t* __restrict__ upd, uint32_t n, uint32_t* __restrict__ cursor,
                                        uint32_t* __restrict__ end)
@@ -220,167 +198,8 @@ int set_error(int code, const char* m) noexcept
 }
 } // namespace ogabi
 
+// ---- samples by name (og_register_sample): the process-wide registry (SampleData: og_engine.h) ------------------------
 namespace {
-
-int set_err(int code, const std::string& m) { return ogabi::set_error(code, m); }
-
-using HipError = ogabi::DeviceError;
-#define HIPCK(expr)                                                                                    \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            throw HipError(std::string(#expr) + ": " + hipGetErrorString(_e));                         \
-    } while (0)
-
-// Host memory this library does not own (a caller's array, a std::vector) never goes to hipMemcpyAsync directly.  For
-// a transfer above a size threshold the runtime pins the pages where they lie (a userptr mapping) and keeps the
-// pinning cached; whenever the kernel later migrates, compacts or unmaps those pages the driver evicts and restores
-// EVERY queue of the process.  Measured through the blocking entry at 4 M / 8 M voices (bench.py's real-time record:
-// the 32 MB frequency array of og_set_voice_values and the event-timeline vectors of the first rebuild were such
-// mappings): one ~23 ms stall of the stream -- several missed audio deadlines -- every few thousand blocks.  So every
-// transfer larger than a staging copy goes through two pinned bounce buffers of this engine's own.
-struct Bounce {
-    static constexpr size_t CHUNK = (size_t)4 << 20, DIRECT = 16384; // (below DIRECT the runtime stages the bytes itself)
-    void* h[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool busy[2] = {false, false};
-    int k = 0;
-    void ensure()
-    {
-        if (h[0]) return;
-        for (int i = 0; i < 2; ++i) {
-            HIPCK(hipHostMalloc(&h[i], CHUNK, hipHostMallocDefault));
-            HIPCK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-        }
-    }
-    // host -> device, asynchronous like hipMemcpyAsync from pinned memory: `src` may be reused when the call returns
-    void h2d(void* dst, const void* src, size_t n, hipStream_t s)
-    {
-        if (n <= DIRECT) {
-            if (n) HIPCK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s));
-            return;
-        }
-        ensure();
-        for (size_t off = 0; off < n; off += CHUNK) {
-            const size_t len = std::min(CHUNK, n - off);
-            if (busy[k]) HIPCK(hipEventSynchronize(ev[k]));
-            memcpy(h[k], (const char*)src + off, len);
-            HIPCK(hipMemcpyAsync((char*)dst + off, h[k], len, hipMemcpyHostToDevice, s));
-            HIPCK(hipEventRecord(ev[k], s));
-            busy[k] = true;
-            k ^= 1;
-        }
-    }
-    // device -> host; the bytes are in `dst` when the call returns (the stream is drained up to the copy)
-    void d2h(void* dst, const void* src, size_t n, hipStream_t s)
-    {
-        if (n <= DIRECT) {
-            if (n) HIPCK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s));
-            HIPCK(hipStreamSynchronize(s));
-            return;
-        }
-        ensure();
-        size_t pend_off[2] = {0, 0}, pend_len[2] = {0, 0};
-        auto land = [&](int i) {
-            if (!pend_len[i]) return;
-            HIPCK(hipEventSynchronize(ev[i]));
-            memcpy((char*)dst + pend_off[i], h[i], pend_len[i]);
-            pend_len[i] = 0;
-            busy[i] = false;
-        };
-        for (int i = 0; i < 2; ++i)
-            if (busy[i]) { // (an upload still reading the buffer)
-                HIPCK(hipEventSynchronize(ev[i]));
-                busy[i] = false;
-            }
-        for (size_t off = 0; off < n; off += CHUNK) {
-            const size_t len = std::min(CHUNK, n - off);
-            land(k);
-            HIPCK(hipMemcpyAsync(h[k], (const char*)src + off, len, hipMemcpyDeviceToHost, s));
-            HIPCK(hipEventRecord(ev[k], s));
-            pend_off[k] = off;
-            pend_len[k] = len;
-            k ^= 1;
-        }
-        land(k);
-        land(k ^ 1);
-    }
-    void release()
-    {
-        for (int i = 0; i < 2; ++i) {
-            if (h[i]) (void)hipHostFree(h[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-            h[i] = nullptr;
-            ev[i] = nullptr;
-        }
-    }
-};
-
-struct Ramp { // ValueRampState  oscen-lib/src/graph/types.rs:300-373
-    float current = 0, target = 0, increment = 0;
-    uint32_t frames_remaining = 0;
-    uint32_t default_frames = 0;
-    bool ramping() const { return frames_remaining > 0; }
-    void set_immediate(float v)
-    {
-        current = target = v;
-        increment = 0.0f;
-        frames_remaining = 0;
-    }
-    void set_with_ramp(float t, uint32_t frames)
-    {
-        if (frames == 0) {
-            set_immediate(t);
-        } else {
-            target = t;
-            increment = (t - current) / (float)frames;
-            frames_remaining = frames;
-        }
-    }
-    bool tick()
-    {
-        if (frames_remaining > 0) {
-            frames_remaining -= 1;
-            if (frames_remaining == 0) {
-                current = target;
-                increment = 0.0f;
-                return true;
-            }
-            current += increment;
-        }
-        return false;
-    }
-};
-
-struct HostEvent { // a push that has not reached the device timeline yet
-    uint32_t voice;
-    uint64_t frame;
-    uint32_t target;
-    float value;
-    uint64_t seq;
-    bool block_local; // pushed relative to the next block (reference try_push semantics)
-};
-
-constexpr int RAMP_RING = 8;
-constexpr int EV_RING = 8;              // pinned staging buffers of the incremental event path
-constexpr size_t EV_STAGE_EVENTS = 131072; // events (and voice updates) one staging buffer holds (8 x 2 MB + 8 x 1.5 MB pinned)
-
-} // namespace
-
-struct og_graph_desc {
-    ogc::GraphDesc g;
-};
-
-// ---- samples by name (og_register_sample): process-wide, beside the impulse responses --------------------------------
-// interleaved frames as registered -- at the graph's rate (og_register_sample: rate 0, untagged) or at their own
-// (og_register_sample_at_rate / og_register_sample_wav: og_load_sample conforms them on the device); a name that exists is
-// replaced (engines that loaded the old one keep their device copy)
-namespace {
-struct SampleData {
-    std::vector<float> interleaved;
-    uint32_t frames = 0, channels = 1;
-    uint32_t rate = 0; // 0: untagged
-};
 // device memory that lives for one call
 struct DeviceScratch {
     float* p = nullptr;
@@ -399,12 +218,14 @@ std::mutex& sample_registry_lock()
     static std::mutex m;
     return m;
 }
+} // namespace
 std::shared_ptr<const SampleData> lookup_sample(const std::string& name)
 {
     std::lock_guard<std::mutex> lk(sample_registry_lock());
     auto it = sample_registry().find(name);
     return it == sample_registry().end() ? nullptr : it->second;
 }
+namespace {
 // SamplePlayerConsumer::build (sample_player/mod.rs:38-50): the source's channels onto a player of `width` channels,
 // frame-major -- one source channel broadcasts, otherwise target channel c takes source channel min(c, src_ch - 1)
 void map_sample_channels(const SampleData& s, uint32_t width, float* dst)
@@ -417,1486 +238,597 @@ void map_sample_channels(const SampleData& s, uint32_t width, float* dst)
 }
 } // namespace
 
-// OSCEN_GPU_HOST_PROF=1: wall time of the host-side phases of the live path, printed when the engine is destroyed
-struct HostProf {
-    enum { SYNC_EVENTS, INCREMENTAL, REBUILD, LAUNCH, RAMPS, EV_WAIT, EV_COMMIT, N };
-    double t[N] = {};
-    uint64_t n[N] = {};
-    bool on = ogabi::experiment_knob("OSCEN_GPU_HOST_PROF") != nullptr;
-    struct Scope {
-        HostProf& p;
-        int k;
-        std::chrono::steady_clock::time_point t0;
-        Scope(HostProf& p_, int k_) : p(p_), k(k_) { if (p.on) t0 = std::chrono::steady_clock::now(); }
-        ~Scope()
-        {
-            if (!p.on) return;
-            p.t[k] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            p.n[k] += 1;
-        }
-    };
-    void report() const
-    {
-        if (!on) return;
-        static const char* names[N] = {"sync_events", "incremental_update", "full_rebuild", "flush_bus (launches)", "ramp table",
-                                        "  staging-slot wait", "  commit + launch"};
-        for (int k = 0; k < N; ++k)
-            if (n[k]) fprintf(stderr, "[oscen_gpu host prof] %-22s %9llu calls %10.1f us total %8.2f us/call\n", names[k],
-                              (unsigned long long)n[k], t[k] * 1e6, t[k] * 1e6 / (double)n[k]);
-    }
-};
-
-struct og_engine {
-    HostProf prof;
-    std::unique_ptr<ogc::CompiledGraph> cg;
-    OgLaunchFn launch = nullptr;
-    OgZeroLaunchFn launch_zero = nullptr; // the zero variant of `launch` (og_graph.cpp, ZeroChain), where the graph has one
-    bool zero_spec = true; // launches may run the graph's zero variant (OSCEN_GPU_ZERO_SPEC=0: never)
-    bool last_zero = false; // the last launch ran a zero variant (og_kernel_name)
-    // the deeper zero variant (og_graph.cpp, ZeroFolds): tier 2 of the registry
-    OgZeroLaunchFn launch_zero2 = nullptr;
-    bool zero2_spec = true; // launches may run it (OSCEN_GPU_ZERO2_SPEC=0, or OSCEN_GPU_ZERO_SPEC=0: never)
-    bool stage_spec = true; // ... with its stage-uniform envelope bodies (OSCEN_GPU_STAGE_SPEC=0: the general quiet bodies only)
-    bool guards_held = true; // every launch so far had finite values in cg->finite_slots: no operator state can hold inf / NaN
-    int last_tier = 0;       // what the last launch ran: 0 general, 1 zero variant, 2 deeper zero variant (og_kernel_fold_tier)
-    std::unique_ptr<OgJitKernel> jit;
-    uint32_t V = 0;
-    int device = 0;
-    float sr = 44100.0f;
-    bool inited = false;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-
-    std::vector<float> values; // per input: plain value, or mirror of ramp.current
-    std::vector<std::vector<float>> stream_blocks; // per input: `<stream_in>_block` (stream inputs only), OG_MAX_BLOCK samples
-    std::vector<Ramp> ramps;   // per input (only meaningful when ramp_row >= 0)
-    uint32_t active_ramps = 0;
-
-    uint32_t n_wg = 0;
-    uint32_t lanes = OG_WAVE;
-    uint32_t split = 0; // pipeline depth of the launched kernel variant: 0 (ordinary), 2 or 4 waves per 64 voices
-    bool wide = false;  // split == 4: the 16-frame hand-off form (og_k4w_*)
-    uint32_t* d_state = nullptr;
-    Bounce bounce; // pinned staging for transfers from / to memory that is not ours
-    uint32_t* d_lane_state = nullptr;
-    float* d_ring[OG_MAX_RINGS] = {nullptr, nullptr, nullptr, nullptr}; // delay lines [capacity][V]
-    uint32_t ring_cap[OG_MAX_RINGS] = {0, 0, 0, 0};
-    float* d_mono = nullptr;      // summed voices before the post-mix stage
-    float* d_bus_phase = nullptr; // Tremolo.phase
-    // ---- post-mix Convolver (og_bus_conv.hip.h) ---------------------------------------------------
-    // A response lives on the device from og_set_bus_ir (or og_create) until the engine is destroyed or a later
-    // og_set_bus_ir finds the stream idle: launches already queued may still read it.
-    struct ConvIR {
-        float* d = nullptr;
-        std::vector<float> taps; // host copy (snapshots)
-        uint32_t K() const { return (uint32_t)taps.size(); }
-    };
-    // what a block is rendered under: the current response and, during the crossfade of a swap, the outgoing one; each with
-    // the frame its history is valid from (a new response only sees input from the swap frame on)
-    struct ConvCfg {
-        std::shared_ptr<ConvIR> cur, old;
-        uint64_t cur_from = 0, old_from = 0, fade_start = 0;
-        bool same(const ConvCfg& o) const
-        {
-            return cur == o.cur && old == o.old && cur_from == o.cur_from && old_from == o.old_from && fade_start == o.fade_start;
-        }
-    };
-    ConvCfg conv;                          // the state after the last queued block
-    std::shared_ptr<ConvIR> conv_pending;  // og_set_bus_ir: takes effect at the first frame of the next block
-    std::vector<ConvCfg> q_conv;           // configurations of the queued blocks (QueuedBlock::conv)
-    std::vector<float*> conv_bufs;         // every device tap buffer this engine holds (conv_gc frees the unused ones)
-    // history: interleaved frames, [hist_len][voice_channels]; the next batch's dry bus goes to frame hist_pos and at least
-    // hist_keep frames in front of it hold the input that came before (zeros before the first block)
-    float* d_hist = nullptr;
-    size_t hist_len = 0, hist_keep = 0, hist_pos = 0;
-    float* d_conv_rows = nullptr; // partial rows: [current | outgoing][segment][channel][conv_row_stride]
-    uint32_t conv_row_stride = 0;
-    size_t conv_rows_half = 0;
-    bool conv_on() const { return cg->bus_stage == ogc::BusStage::Convolver && bus_stage; }
-    uint32_t conv_fade_len() const { return (uint32_t)std::max(1.0f, roundf(0.02f * sr)); } // prepare(): CROSSFADE_SECONDS * sr, rounded, >= 1
-    std::shared_ptr<ConvIR> conv_upload(const float* taps, size_t n)
-    {
-        auto ir = std::make_shared<ConvIR>();
-        ir->taps.assign(taps, taps + n);
-        if (n) {
-            HIPCK(hipMalloc(&ir->d, n * 4));
-            conv_bufs.push_back(ir->d);
-            bounce.h2d(ir->d, ir->taps.data(), n * 4, stream);
-        }
-        return ir;
-    }
-    void conv_retire(std::shared_ptr<ConvIR>& ir) { ir.reset(); }
-    void conv_gc() // free the taps no response in use points at; only with nothing queued and the stream idle
-    {
-        if (!queue.empty() || hipStreamQuery(stream) != hipSuccess) return;
-        std::vector<float*> keep;
-        for (float* p : conv_bufs) {
-            bool used = false;
-            for (const ConvIR* ir : {conv.cur.get(), conv.old.get(), conv_pending.get()}) used = used || (ir && ir->d == p);
-            if (used) keep.push_back(p);
-            else (void)hipFree(p);
-        }
-        conv_bufs.swap(keep);
-    }
-    // (re)size the history and the partial rows for responses of up to need_hist + 1 taps and the current batch size,
-    // keeping the history; the stream is idle (callers launch the queue and wait first)
-    void conv_alloc(size_t need_hist)
-    {
-        const size_t vc = cg->voice_channels;
-        const size_t max_frames = (size_t)OG_MAX_BLOCK * batch_cap;
-        const size_t keep = std::max(hist_keep, (std::max<size_t>(need_hist, 1) + OG_CONV_S - 1) / OG_CONV_S * OG_CONV_S);
-        const size_t len = 2 * keep + 2 * max_frames;
-        if (!d_hist || keep != hist_keep || len != hist_len) {
-            float* n = nullptr;
-            HIPCK(hipMalloc(&n, len * vc * 4));
-            HIPCK(hipMemsetAsync(n, 0, len * vc * 4, stream));
-            if (d_hist) {
-                HIPCK(hipMemcpyAsync(n + (keep - hist_keep) * vc, d_hist + (hist_pos - hist_keep) * vc, hist_keep * vc * 4, hipMemcpyDeviceToDevice, stream));
-                HIPCK(hipStreamSynchronize(stream));
-                HIPCK(hipFree(d_hist));
-            }
-            d_hist = n;
-            hist_keep = keep;
-            hist_len = len;
-            hist_pos = keep;
-        }
-        const uint32_t stride = (uint32_t)((max_frames + 3) / 4 * 4);
-        const size_t half = (keep / OG_CONV_S + 1) * vc * stride;
-        if (!d_conv_rows || stride != conv_row_stride || half != conv_rows_half) {
-            if (d_conv_rows) HIPCK(hipFree(d_conv_rows));
-            d_conv_rows = nullptr;
-            HIPCK(hipMalloc(&d_conv_rows, 2 * half * 4));
-            conv_row_stride = stride;
-            conv_rows_half = half;
-        }
-        HIPCK(hipStreamSynchronize(stream));
-    }
-    void conv_reset() // prepare(): cleared history, no fade; the current response stays
-    {
-        if (!d_hist) return;
-        HIPCK(hipMemsetAsync(d_hist, 0, hist_len * cg->voice_channels * 4, stream));
-        hist_pos = hist_keep;
-        conv_retire(conv.old);
-        conv.cur_from = conv.old_from = conv.fade_start = 0;
-        q_conv.clear();
-    }
-    // ---- SamplePlayer: the device sample pool ------------------------------------------------------------------------
-    // og_load_sample appends a sample to the pool once per width the graph's players have (the reference's Vec<F>,
-    // frame-major) and gives it the next index; the descriptor table [player][sample_cap]{offset in floats, frames} is what
-    // the kernels read once per launch.  Growing either waits for the stream (not an audio-thread call).  Publishing
-    // (og_set_sample / og_set_voice_samples) writes the players' two state words behind the queued blocks.
-    struct LoadedSample {
-        std::string name;
-        uint32_t frames = 0, channels = 0; // the source's shape (snapshots check it)
-        uint32_t src_rate = 0;             // the source's rate tag (0: untagged, never checked)
-        uint32_t rate = 0;                 // tagged: the graph rate it was conformed to ...
-        uint32_t pool_frames = 0;          // ... and its length in the pool (untagged: `frames`)
-        uint32_t off[5] = {0, 0, 0, 0, 0}; // [width]: offset of the width's copy in the pool, in floats
-    };
-    // the graph rate a tagged sample is conformed to: og_init's, a positive integer (AudioAsset's rates are u32)
-    uint32_t graph_rate(const char* who) const
-    {
-        if (!inited) throw ogabi::Error(OG_E_INVALID, std::string(who) + ": the graph rate is not set yet (og_init comes first for a sample registered at a rate)");
-        if (!(sr >= 1.0f && sr < 4294967296.0f && sr == floorf(sr)))
-            throw ogabi::Error(OG_E_INVALID, std::string(who) + ": a sample registered at a rate needs an engine rate that is a positive integer, this engine runs at " + std::to_string(sr));
-        return (uint32_t)sr;
-    }
-    // the length a tagged sample has once conformed to `dst` (the checks of from_samples behind the resample)
-    static uint32_t conformed_frames(const std::string& name, const SampleData& sd, uint32_t dst)
-    {
-        if (sd.rate == dst) return sd.frames;
-        const OgResamplePlan p = og_resample_plan(sd.frames, sd.rate, dst);
-        if (p.out_len == 0)
-            throw ogabi::Error(OG_E_INVALID, "sample '" + name + "' (" + std::to_string(sd.frames) + " frames at " + std::to_string(sd.rate) + ") is empty once conformed to " + std::to_string(dst));
-        if (p.out_len >= ((uint64_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
-        return (uint32_t)p.out_len;
-    }
-    std::vector<LoadedSample> samples;
-    float* d_pool = nullptr;
-    size_t pool_used = 0, pool_cap = 0; // floats
-    uint32_t* d_desc = nullptr;
-    uint32_t sample_cap = 0; // entries per player in d_desc
-    void pool_reserve(size_t need)
-    {
-        if (need <= pool_cap) return;
-        const size_t cap = std::max(need, std::max<size_t>(2 * pool_cap, (size_t)1 << 16));
+// ---- og_engine: the methods that launch kernels or use the device headers above ---------------------------------------
+// (re)size the history and the partial rows for responses of up to need_hist + 1 taps and the current batch size,
+// keeping the history; the stream is idle (callers launch the queue and wait first)
+void og_engine::conv_alloc(size_t need_hist)
+{
+    const size_t vc = cg->voice_channels;
+    const size_t max_frames = (size_t)OG_MAX_BLOCK * batch_cap;
+    const size_t keep = std::max(hist_keep, (std::max<size_t>(need_hist, 1) + OG_CONV_S - 1) / OG_CONV_S * OG_CONV_S);
+    const size_t len = 2 * keep + 2 * max_frames;
+    if (!d_hist || keep != hist_keep || len != hist_len) {
         float* n = nullptr;
-        HIPCK(hipMalloc(&n, cap * 4));
-        if (pool_used) HIPCK(hipMemcpyAsync(n, d_pool, pool_used * 4, hipMemcpyDeviceToDevice, stream));
-        HIPCK(hipStreamSynchronize(stream));
-        if (d_pool) HIPCK(hipFree(d_pool));
-        d_pool = n;
-        pool_cap = cap;
-    }
-    void upload_desc() // the whole table: a few words per sample
-    {
-        const size_t np = cg->players.size();
-        if (samples.size() > sample_cap) {
-            const uint32_t cap = std::max<uint32_t>(16u, 2u * (uint32_t)samples.size());
-            if (d_desc) HIPCK(hipFree(d_desc));
-            d_desc = nullptr;
-            sample_cap = 0;
-            HIPCK(hipMalloc(&d_desc, np * cap * 2 * 4));
-            sample_cap = cap;
-        }
-        std::vector<uint32_t> tab(np * sample_cap * 2, 0u);
-        for (size_t k = 0; k < np; ++k)
-            for (size_t i = 0; i < samples.size(); ++i) {
-                tab[2 * (k * sample_cap + i)] = samples[i].off[cg->players[k].channels];
-                tab[2 * (k * sample_cap + i) + 1] = samples[i].pool_frames;
-            }
-        bounce.h2d(d_desc, tab.data(), tab.size() * 4, stream);
-        HIPCK(hipStreamSynchronize(stream));
-    }
-    // brings a registered sample onto the device (every width the players have); returns its index
-    uint32_t load_sample(const std::string& name, const SampleData& sd)
-    {
-        flush_bus();
-        HIPCK(hipStreamSynchronize(stream)); // (launches in flight read the pool and the table)
-        LoadedSample ls;
-        ls.name = name;
-        ls.frames = sd.frames;
-        ls.channels = sd.channels;
-        ls.src_rate = sd.rate;
-        ls.rate = sd.rate ? graph_rate("og_load_sample") : 0u;
-        ls.pool_frames = sd.rate ? conformed_frames(name, sd, ls.rate) : sd.frames;
-        const bool conform = sd.rate && sd.rate != ls.rate; // (an equal rate takes the untagged path)
-        bool widths[5] = {false, false, false, false, false};
-        size_t need = pool_used;
-        for (const auto& pl : cg->players)
-            if (!widths[pl.channels]) {
-                widths[pl.channels] = true;
-                need += (size_t)ls.pool_frames * pl.channels;
-            }
-        if (need >= ((size_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
-        pool_reserve(need);
-        if (conform) { // the source goes up once; conformed and mapped on the device, straight into the pool
-            const OgResamplePlan plan = og_resample_plan(sd.frames, sd.rate, ls.rate);
-            DeviceScratch d_src(sd.interleaved.size()), d_conf((size_t)ls.pool_frames * sd.channels);
-            bounce.h2d(d_src.p, sd.interleaved.data(), sd.interleaved.size() * 4, stream);
-            og_resample_launch(d_src.p, sd.frames, sd.channels, plan, d_conf.p, stream);
-            for (uint32_t w = 1; w <= 4; ++w) {
-                if (!widths[w]) continue;
-                ls.off[w] = (uint32_t)pool_used;
-                og_map_channels_launch(d_conf.p, ls.pool_frames, sd.channels, w, d_pool + pool_used, stream);
-                pool_used += (size_t)ls.pool_frames * w;
-            }
-            HIPCK(hipGetLastError());
+        HIPCK(hipMalloc(&n, len * vc * 4));
+        HIPCK(hipMemsetAsync(n, 0, len * vc * 4, stream));
+        if (d_hist) {
+            HIPCK(hipMemcpyAsync(n + (keep - hist_keep) * vc, d_hist + (hist_pos - hist_keep) * vc, hist_keep * vc * 4, hipMemcpyDeviceToDevice, stream));
             HIPCK(hipStreamSynchronize(stream));
+            HIPCK(hipFree(d_hist));
         }
-        std::vector<float> mapped;
-        for (uint32_t w = 1; w <= 4 && !conform; ++w) {
+        d_hist = n;
+        hist_keep = keep;
+        hist_len = len;
+        hist_pos = keep;
+    }
+    const uint32_t stride = (uint32_t)((max_frames + 3) / 4 * 4);
+    const size_t half = (keep / OG_CONV_S + 1) * vc * stride;
+    if (!d_conv_rows || stride != conv_row_stride || half != conv_rows_half) {
+        if (d_conv_rows) HIPCK(hipFree(d_conv_rows));
+        d_conv_rows = nullptr;
+        HIPCK(hipMalloc(&d_conv_rows, 2 * half * 4));
+        conv_row_stride = stride;
+        conv_rows_half = half;
+    }
+    HIPCK(hipStreamSynchronize(stream));
+}
+
+// the length a tagged sample has once conformed to `dst` (the checks of from_samples behind the resample)
+uint32_t og_engine::conformed_frames(const std::string& name, const SampleData& sd, uint32_t dst)
+{
+    if (sd.rate == dst) return sd.frames;
+    const OgResamplePlan p = og_resample_plan(sd.frames, sd.rate, dst);
+    if (p.out_len == 0)
+        throw ogabi::Error(OG_E_INVALID, "sample '" + name + "' (" + std::to_string(sd.frames) + " frames at " + std::to_string(sd.rate) + ") is empty once conformed to " + std::to_string(dst));
+    if (p.out_len >= ((uint64_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
+    return (uint32_t)p.out_len;
+}
+
+// brings a registered sample onto the device (every width the players have); returns its index
+uint32_t og_engine::load_sample(const std::string& name, const SampleData& sd)
+{
+    flush_bus();
+    HIPCK(hipStreamSynchronize(stream)); // (launches in flight read the pool and the table)
+    LoadedSample ls;
+    ls.name = name;
+    ls.frames = sd.frames;
+    ls.channels = sd.channels;
+    ls.src_rate = sd.rate;
+    ls.rate = sd.rate ? graph_rate("og_load_sample") : 0u;
+    ls.pool_frames = sd.rate ? conformed_frames(name, sd, ls.rate) : sd.frames;
+    const bool conform = sd.rate && sd.rate != ls.rate; // (an equal rate takes the untagged path)
+    bool widths[5] = {false, false, false, false, false};
+    size_t need = pool_used;
+    for (const auto& pl : cg->players)
+        if (!widths[pl.channels]) {
+            widths[pl.channels] = true;
+            need += (size_t)ls.pool_frames * pl.channels;
+        }
+    if (need >= ((size_t)1 << 32)) throw ogabi::Error(OG_E_NOMEM, "og_load_sample: the engine's sample pool is limited to 2^32 floats");
+    pool_reserve(need);
+    if (conform) { // the source goes up once; conformed and mapped on the device, straight into the pool
+        const OgResamplePlan plan = og_resample_plan(sd.frames, sd.rate, ls.rate);
+        DeviceScratch d_src(sd.interleaved.size()), d_conf((size_t)ls.pool_frames * sd.channels);
+        bounce.h2d(d_src.p, sd.interleaved.data(), sd.interleaved.size() * 4, stream);
+        og_resample_launch(d_src.p, sd.frames, sd.channels, plan, d_conf.p, stream);
+        for (uint32_t w = 1; w <= 4; ++w) {
             if (!widths[w]) continue;
             ls.off[w] = (uint32_t)pool_used;
-            mapped.resize((size_t)sd.frames * w);
-            map_sample_channels(sd, w, mapped.data());
-            if (!mapped.empty()) bounce.h2d(d_pool + pool_used, mapped.data(), mapped.size() * 4, stream);
-            HIPCK(hipStreamSynchronize(stream));
-            pool_used += mapped.size();
+            og_map_channels_launch(d_conf.p, ls.pool_frames, sd.channels, w, d_pool + pool_used, stream);
+            pool_used += (size_t)ls.pool_frames * w;
         }
-        samples.push_back(ls);
-        upload_desc();
-        return (uint32_t)samples.size() - 1;
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(stream));
     }
-    int find_player(const char* node) const
-    {
-        std::string p; // the spelling of og_read_state_field paths: `inner.player` -> `inner_player`
-        for (const char* c = node; *c; ++c) {
-            if (*c == '[') p += "__";
-            else if (*c == '.') p.push_back('_');
-            else if (*c != ']' && !isspace((unsigned char)*c)) p.push_back(*c);
-        }
-        for (size_t k = 0; k < cg->players.size(); ++k)
-            if (cg->players[k].name == p) return (int)k;
-        return -1;
+    std::vector<float> mapped;
+    for (uint32_t w = 1; w <= 4 && !conform; ++w) {
+        if (!widths[w]) continue;
+        ls.off[w] = (uint32_t)pool_used;
+        mapped.resize((size_t)sd.frames * w);
+        map_sample_channels(sd, w, mapped.data());
+        if (!mapped.empty()) bounce.h2d(d_pool + pool_used, mapped.data(), mapped.size() * 4, stream);
+        HIPCK(hipStreamSynchronize(stream));
+        pool_used += mapped.size();
     }
-    OgEvent* d_events = nullptr;
-    size_t ev_cap = 0;
-    size_t ev_headroom_env = 0; // OSCEN_GPU_EV_HEADROOM at og_create (0 = unset)
-    size_t ev_reserve = 0; // og_reserve_events: room kept behind a bulk score for live segments
-    uint32_t* d_ev_end = nullptr;
-    uint32_t* d_ev_cursor = nullptr;
-    float* d_partials = nullptr;
-    float* d_partials2 = nullptr; // group sums of the multi-pass bus reduce
-    // ADSR release reciprocals (OgBlockArgs::rcp_tab): entries 1 .. rcp_n, grown (never per block: at least doubled) when a
-    // launch's longest release needs more; a replaced table stays allocated until og_destroy -- launches already queued may
-    // still read it -- so that growing never waits for the device.  Launches whose release exceeds rcp_cap (OG_RCP_MAX;
-    // experiment knob OSCEN_GPU_RCP_CAP) run the v_rcp_f32 bodies.
-    float* d_rcp = nullptr;
-    uint32_t rcp_n = 0;
-    uint32_t rcp_cap = OG_RCP_MAX;
-    std::vector<float*> rcp_old;
-    // Block queue (og_set_bus_batching): up to `bus_batch` consecutive async blocks that nothing separates (no value
-    // change, no event push, no taps) are rendered by ONE launch of the voice kernel over their frames back to back --
-    // state loaded and stored once, one inter-kernel gap, one bus reduce per tree level -- instead of one launch each.
-    // A queued block has had its ramps ticked and its stream samples captured; anything that touches engine state
-    // launches the queue first.  Results are those of block-by-block processing, bit for bit.
-    std::vector<uint32_t> tap_voices; // og_set_voice_taps: the tapped voices by the caller's numbers (slots are resolved from them)
-    uint32_t bus_batch = 1; // queue limit (blocks per launch)
-    uint32_t batch_cap = 1; // what the buffers are sized for
-    struct QueuedBlock {
-        float* dst; // where the block's bus goes
-        uint32_t frames;
-        float trem_rate, trem_depth;
-        uint32_t conv; // index into q_conv (post-mix Convolver)
-    };
-    std::vector<QueuedBlock> queue;
-    uint64_t q_frame0 = 0;   // absolute frame of the first queued block
-    uint32_t q_frames = 0;   // frames queued
-    bool q_ramps = false;    // some queued block ticked a ramp (or the graph has stream inputs): table-reading variant
-    int q_ramp_slot = -1;    // staging buffer of the per-frame table being filled
-    float* d_stage_bus = nullptr; // bus of a launch whose blocks' destinations are not contiguous
-    float* d_bus = nullptr;
-    float* d_ramp[RAMP_RING] = {};
-    float* h_ramp[RAMP_RING] = {};
-    uint64_t ramp_seq[RAMP_RING] = {}; // batch whose launch copied ramp table i to the device (0 = never)
-    int ramp_head = 0;
-    // events leaving the voices (graph event outputs) and pushes the in-voice queues dropped: device log / counter
-    OgOutEvent* d_out_ev = nullptr;
-    uint32_t* d_out_ev_count = nullptr; // [0] = events appended, [1] = in-voice pushes lost
-    uint32_t out_ev_cap = 0;
-    uint64_t out_ev_overflow = 0;       // events that did not fit the log (reported by og_read_output_events)
-    uint64_t ev_lost_total = 0;         // in-voice pushes lost, read back so far
-    std::vector<OgOutEvent> out_ev_carry; // og_read_output_events: drained from the device log, not yet handed out
-    float* d_taps = nullptr;
-    int32_t* d_tap_slot = nullptr;
-    uint32_t n_taps = 0;
-    uint32_t last_frames = 0;
+    samples.push_back(ls);
+    upload_desc();
+    return (uint32_t)samples.size() - 1;
+}
 
-    // ---- event timeline ---------------------------------------------------------------------------
-    // Device: d_events holds every voice's unconsumed events as one segment [cursor, end), sorted by
-    // (frame, push order).  A full rebuild lays the segments out in voice order (CSR) and uploads
-    // O(V) words; the incremental path (live pushes: og_push_voice_event / MIDI) appends a new segment
-    // for each voice that received events -- its unconsumed old events merged with the new ones -- at the
-    // tail of d_events and repoints that voice's (cursor, end) with a tiny kernel: O(#pushes) host work,
-    // one async copy from a pinned staging ring, no stream synchronisation.
-    std::vector<HostEvent> pending;      // pushes not yet on the device timeline (PHYSICAL voice slots)
-    // og_group_voices: logical voice (what every entry point takes and hands out) -> physical slot (what the device arrays
-    // and everything below the entry points index).  Empty = identity.
-    std::vector<uint32_t> phys_of, logical_of;
-    uint32_t phys(uint32_t v) const { return phys_of.empty() ? v : phys_of[v]; }
-    uint32_t logical(uint32_t p) const { return logical_of.empty() ? p : logical_of[p]; }
-    std::vector<OgEvent> h_events;       // host mirror of d_events (the whole ring)
-    std::vector<uint32_t> seg_begin, seg_end; // per voice: its current segment (empty vectors = all segments empty)
-    std::vector<uint64_t> seg_last;           // per voice: frame of the segment's last event (< frame_now: all consumed)
-    // Continuation (round 6): on the HOST a voice's timeline is its segment [seg_begin, seg_end) followed by
-    // [cont_begin, cont_end) -- the tail of an EARLIER segment left where it lies in the ring.  A live push onto a voice with
-    // a long score ahead of it writes a new segment {what is due up to the end of the launch being prepared, merged with the
-    // pushes} and remembers the rest as the continuation; every frame in the segment is < every frame in the continuation.
-    // The device knows nothing of this (one segment per voice, as ever -- a first form that taught the kernels to hop cost
-    // the four-wave kernel 4 % and the ordinary one 30 spills): before the launch in which a continuation's first event is
-    // due the host points the voice at it -- a 12-byte cursor update when the segment in front has been played, which is
-    // the usual case (incremental_update / merge_voice).  Cost of a message: its own records, whatever the score's length.
-    // Vectors are empty until a continuation exists; `cont_due` orders the voices by their continuation's first frame.
-    std::vector<uint32_t> cont_begin, cont_end;
-    std::vector<uint64_t> cont_last;
-    uint64_t n_events_copied = 0; // events written to the ring by incremental updates (old ones carried over + new ones)
-    std::vector<std::pair<uint64_t, uint32_t>> cont_due; // min-heap of {first frame of the continuation, voice}; stale entries are skipped
-    void cont_due_push(uint32_t v)
-    {
-        cont_due.emplace_back(h_events[cont_begin[v]].frame, v);
-        std::push_heap(cont_due.begin(), cont_due.end(), std::greater<std::pair<uint64_t, uint32_t>>());
+og_engine::~og_engine()
+{
+    prof.report();
+    (void)hipSetDevice(device);
+    // a borrowed stream (og_set_stream) may already be gone: wait for the device instead of touching it
+    if (own_stream && stream) (void)hipStreamSynchronize(stream);
+    else (void)hipDeviceSynchronize();
+    bounce.release();
+    (void)hipFree(d_state);
+    (void)hipFree(d_lane_state);
+    for (int k = 0; k < OG_MAX_RINGS; ++k) (void)hipFree(d_ring[k]);
+    (void)hipFree(d_mono);
+    (void)hipFree(d_bus_phase);
+    (void)hipFree(d_hist);
+    (void)hipFree(d_conv_rows);
+    for (float* p : conv_bufs) (void)hipFree(p);
+    (void)hipFree(d_events);
+    (void)hipFree(d_ev_end);
+    (void)hipFree(d_ev_cursor);
+    (void)hipFree(d_partials);
+    (void)hipFree(d_partials2);
+    (void)hipFree(d_rcp);
+    (void)hipFree(d_pool);
+    (void)hipFree(d_desc);
+    for (float* p : rcp_old) (void)hipFree(p);
+    (void)hipFree(d_stage_bus);
+    (void)hipFree(d_bus);
+    (void)hipFree(d_taps);
+    (void)hipFree(d_tap_slot);
+    (void)hipFree(d_out_ev);
+    (void)hipFree(d_out_ev_count);
+    for (int i = 0; i < RAMP_RING; ++i) {
+        (void)hipFree(d_ramp[i]);
+        if (h_ramp[i]) (void)hipHostFree(h_ramp[i]);
     }
-    // end of the launch that is being prepared: everything before it must be in the voices' segments
-    uint64_t launch_end() const { return queue.empty() ? frame_now : q_frame0 + q_frames; }
-    bool continuation_due() const { return !cont_due.empty() && cont_due.front().first < launch_end(); }
-    // A rest shorter than this is carried over with the merge: copying a kilobyte costs less than the bookkeeping of a
-    // continuation (a heap entry, a second cursor update, two more looks into the cold host mirror) -- measured on the loaded
-    // real-time banks, whose 1 s scores leave ~14 events per voice: with continuations for those p99 rose from 2.29 to
-    // 2.69 ms at 4 194 304 voices (gpurun r06q).
-    static constexpr uint32_t CONT_MIN = 64;
-    size_t n_conts = 0; // voices that have a continuation right now (0: nobody looks at the cont_* arrays -- cold memory)
-    bool has_cont(uint32_t v) const { return n_conts != 0 && cont_begin[v] != cont_end[v]; }
-    void set_cont(uint32_t v, uint32_t b, uint32_t e)
-    {
-        const bool had = cont_begin[v] != cont_end[v];
-        cont_begin[v] = b;
-        cont_end[v] = e;
-        if (b != e) cont_last[v] = h_events[e - 1].frame;
-        n_conts += (b != e ? 1 : 0);
-        n_conts -= (had ? 1 : 0);
+    for (int i = 0; i < EV_RING; ++i) {
+        if (h_stage_ev[i]) (void)hipHostFree(h_stage_ev[i]);
+        if (h_stage_upd[i]) (void)hipHostFree(h_stage_upd[i]);
+        (void)hipFree(d_stage_upd[i]);
     }
-    void ensure_cont() // (sized with the segment arrays, outside the real-time path: 16 bytes per voice of zero-fill)
-    {
-        if (cont_begin.empty()) {
-            cont_begin.assign(V, 0);
-            cont_end.assign(V, 0);
-            cont_last.assign(V, 0);
-        }
-    }
-    // events of one segment are sorted by frame: first index in [b, e) whose frame is >= fr / > fr
-    uint32_t lower_frame(uint32_t b, uint32_t e, uint64_t fr) const
-    {
-        while (b < e) {
-            const uint32_t m = b + (e - b) / 2;
-            if (h_events[m].frame < fr) b = m + 1;
-            else e = m;
-        }
-        return b;
-    }
-    uint32_t upper_frame(uint32_t b, uint32_t e, uint64_t fr) const
-    {
-        while (b < e) {
-            const uint32_t m = b + (e - b) / 2;
-            if (h_events[m].frame <= fr) b = m + 1;
-            else e = m;
-        }
-        return b;
-    }
-    // the unconsumed part of the voice's segment / of its continuation, as index ranges of h_events
-    void unconsumed_ranges(uint32_t v, uint64_t hz, uint32_t& hb, uint32_t& he, uint32_t& cb, uint32_t& ce) const
-    {
-        hb = he = cb = ce = 0;
-        if (seg_begin.empty()) return;
-        if (seg_begin[v] != seg_end[v] && seg_last[v] >= hz) {
-            hb = lower_frame(seg_begin[v], seg_end[v], hz);
-            he = seg_end[v];
-        }
-        if (has_cont(v) && cont_last[v] >= hz) {
-            cb = lower_frame(cont_begin[v], cont_end[v], hz);
-            ce = cont_end[v];
-        }
-    }
-    std::vector<uint32_t> grp_head, grp_tail, grp_next, grp_voices; // incremental path: pending events chained per voice
-    std::vector<uint8_t> local_cnt;      // [voice * n_event_inputs + event input]: try_push'ed events queued for the next block
-    std::vector<uint32_t> local_touched; // entries of local_cnt to clear when the block starts
-    size_t ev_tail = 0;                  // next free slot of d_events
-    // d_events is a RING for the live path: segments are appended at ev_tail; a segment is dead once its voice has been
-    // given a newer one or its last event lies before the consumed horizon, and the space of the dead segments at the
-    // front is reused when the tail reaches the end of the buffer -- a steady stream of live pushes (MIDI playing)
-    // never triggers the O(V) rebuild + stream synchronise that a bump pointer needs for compaction (measured: a
-    // 7 ms stall every ~1 400 blocks at 1 M voices, a missed audio deadline).  Only a segment that stays alive at the
-    // front for a whole lap (an event scheduled far ahead) still forces a rebuild.
-    struct RingSeg {
-        uint32_t voice, begin, end;
-    };
-    std::deque<RingSeg> ring_live; // live segments in append order (oldest first)
-    uint64_t n_ring_wraps = 0;
-    // where `n` events can be appended, or SIZE_MAX when the ring is full
-    size_t ring_alloc(size_t n)
-    {
-        size_t at = ring_alloc_bounded(n, 4096);
-        if (at == SIZE_MAX) at = ring_alloc_bounded(n, SIZE_MAX); // (no room behind a bounded sweep: finish it, then decide)
-        return at;
-    }
-    // `sweep` bounds how many dead segments one call retires.  When a long resident score runs out, the segments of ALL
-    // voices die within a few blocks: retiring millions of them in one call was a 10-15 ms stall on the real-time path
-    // (round 4, the loaded bank: one block near the end of every run at 4-8 M voices); the room they occupy is not needed
-    // at once, so the sweep is spread over the following calls.
-    size_t ring_alloc_bounded(size_t n, size_t sweep)
-    {
-        const uint64_t hz = consumed_horizon();
-        while (!ring_live.empty() && sweep-- > 0) {
-            const RingSeg& f = ring_live.front();
-            // alive: the voice's current segment, or the segment its continuation lies in, with something left to play
-            // (a voice that was pointed at its continuation plays a sub-range of the older segment the continuation lay in)
-            // (seg_begin first: a superseded segment -- the usual one at the front -- is settled by that one cold word, as ever)
-            const uint32_t sb = seg_begin[f.voice];
-            const bool is_head = sb >= f.begin && sb < f.end && seg_end[f.voice] <= f.end && sb != seg_end[f.voice] && seg_last[f.voice] >= hz;
-            const bool holds_cont = has_cont(f.voice) && cont_begin[f.voice] >= f.begin && cont_end[f.voice] <= f.end && cont_last[f.voice] >= hz;
-            const bool dead = !is_head && !holds_cont;
-            if (!dead) break;
-            ring_live.pop_front();
-        }
-        if (ring_live.empty()) {
-            ev_tail = 0;
-            return n <= ev_cap ? 0 : SIZE_MAX;
-        }
-        const size_t head = ring_live.front().begin;
-        if (ev_tail >= head) { // live data is [head, tail): room behind the tail, or -- wrapping -- in front of the head
-            if (ev_tail + n <= ev_cap) return ev_tail;
-            if (n < head) {
-                n_ring_wraps += 1;
-                return 0;
-            }
-            return SIZE_MAX;
-        }
-        return ev_tail + n < head ? ev_tail : SIZE_MAX; // wrapped: the tail runs up to the head
-    }
-    bool ev_rebuild = false;             // next block must rebuild the whole timeline
-    void sync_lost_counter(); // device "lost pushes" counter -> ev_lost_total (synchronises the stream)
-    OgEvent* h_stage_ev[EV_RING] = {};   // pinned
-    uint32_t* h_stage_upd[EV_RING] = {}; // pinned, n x {voice, cursor, end}
-    uint32_t* d_stage_upd[EV_RING] = {};
-    uint64_t stage_seq[EV_RING] = {};         // batch (flush_seq) whose launch read staging slot i (0 = never used)
-    uint64_t flush_seq = 0;                    // batches launched so far
-    bool batch_staged = false;                 // the batch being assembled reads a host staging buffer
-    volatile uint64_t* h_progress = nullptr;  // pinned: number of the last batch the stream has finished (og_stream_mark)
-    float* h_bus_pinned = nullptr; // pinned + device-visible: destination of a blocking block's bus (og_process_block)
-    bool blocking_memcpy = false; // OSCEN_GPU_BLOCKING_MEMCPY (A/B knob), read once at og_create
-    uint64_t blocking_waits = 0, blocking_timeouts = 0; // og_process_block calls / calls whose marker wait timed out
-    bool wait_progress(uint64_t seq) // false: the stream was found finished before the marker was seen
-    {
-        // the batch is tens of microseconds long: spin on the marker word (a runtime wait costs more than the block).
-        // A marker that does not show is rare (twice in 44 000 blocks of 4 M voices, both a 20-30 ms block under the
-        // earlier "give it 20 ms, then hipStreamSynchronize" rule): from 256 us on the stream itself is asked every
-        // 128 us (hipStreamQuery does not block), so a late marker costs a fraction of a block, not several deadlines.
-        using clk = std::chrono::steady_clock;
-        const auto t0 = clk::now();
-        auto next_query = t0 + std::chrono::microseconds(256);
-        for (uint32_t spins = 0; !h_progress || *h_progress < seq; ++spins) {
-            if ((spins & 255u) == 255u) {
-                const auto now = clk::now();
-                if (now >= next_query) {
-                    const hipError_t q = hipStreamQuery(stream);
-                    if (q == hipSuccess) return h_progress && *h_progress >= seq;
-                    if (q != hipErrorNotReady) HIPCK(q);
-                    next_query = now + std::chrono::microseconds(128);
-                }
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        return true;
-    }
-    bool batch_done(uint64_t seq)
-    {
-        if (seq == 0 || (h_progress && *h_progress >= seq)) return true;
-        if (seq > flush_seq) return true; // (staged for a batch that was never launched: nothing read it)
-        HIPCK(hipStreamSynchronize(stream)); // (a ring slot that is still in flight: never seen in practice)
-        return true;
-    }
-    int stage_head = 0;
-    uint64_t n_full_rebuilds = 0, n_incremental = 0;
-    size_t n_block_local = 0; // events pushed with try_push semantics for the next block
-    size_t local_from = 0;    // index in `pending` of the first push since the previous block was queued
-    uint64_t seq = 0;
-    uint32_t bus_passes = 0; // og_bus_reduce launches of the last block (1 + levels of the multi-pass tree)
-    uint64_t frame_now = 0;
-    uint64_t dropped = 0;
+    if (h_progress) (void)hipHostFree((void*)h_progress);
+    if (h_bus_pinned) (void)hipHostFree(h_bus_pinned);
+    if (h_clock) (void)hipHostFree(h_clock);
+    for (auto ev : t_start) (void)hipEventDestroy(ev);
+    for (auto ev : t_stop) (void)hipEventDestroy(ev);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
 
-    bool bus_stage = true; // run the post-mix node (Tremolo) here; a cluster shard hands over the mono sum instead
-
-    bool timing = false;
-    std::vector<hipEvent_t> t_start, t_stop;
-    unsigned long long* h_clock = nullptr; // pinned, [T_CLOCK][4]: {cycles, ticks} at the start and at the end of timed launch i
-    static constexpr size_t T_CLOCK = 8192;
-    size_t t_used = 0;
-    size_t t_blocks = 0; // blocks the timed launches covered
-    double last_clock_ghz = 0.0;
-
-    ~og_engine()
-    {
-        prof.report();
-        (void)hipSetDevice(device);
-        // a borrowed stream (og_set_stream) may already be gone: wait for the device instead of touching it
-        if (own_stream && stream) (void)hipStreamSynchronize(stream);
-        else (void)hipDeviceSynchronize();
-        bounce.release();
-        (void)hipFree(d_state);
-        (void)hipFree(d_lane_state);
-        for (int k = 0; k < OG_MAX_RINGS; ++k) (void)hipFree(d_ring[k]);
-        (void)hipFree(d_mono);
-        (void)hipFree(d_bus_phase);
-        (void)hipFree(d_hist);
-        (void)hipFree(d_conv_rows);
-        for (float* p : conv_bufs) (void)hipFree(p);
-        (void)hipFree(d_events);
-        (void)hipFree(d_ev_end);
-        (void)hipFree(d_ev_cursor);
-        (void)hipFree(d_partials);
-        (void)hipFree(d_partials2);
-        (void)hipFree(d_rcp);
-        (void)hipFree(d_pool);
-        (void)hipFree(d_desc);
-        for (float* p : rcp_old) (void)hipFree(p);
-        (void)hipFree(d_stage_bus);
-        (void)hipFree(d_bus);
-        (void)hipFree(d_taps);
-        (void)hipFree(d_tap_slot);
-        (void)hipFree(d_out_ev);
-        (void)hipFree(d_out_ev_count);
-        for (int i = 0; i < RAMP_RING; ++i) {
-            (void)hipFree(d_ramp[i]);
-            if (h_ramp[i]) (void)hipHostFree(h_ramp[i]);
+void og_engine::upload_initial_state()
+{
+    const size_t nw = cg->state.size();
+    std::vector<uint32_t> img(nw * (size_t)V);
+    ogc::UEnv e = env();
+    for (size_t w = 0; w < nw; ++w) {
+        const uint32_t bits = cg->state[w].init(e);
+        std::fill(img.begin() + w * V, img.begin() + (w + 1) * V, bits);
+    }
+    bounce.h2d(d_state, img.data(), img.size() * 4, stream);
+    std::vector<uint32_t> limg;
+    if (!cg->lane_state.empty()) {
+        const size_t per = (size_t)V * cg->lpv * cg->lane_width;
+        limg.resize(cg->lane_state.size() * per);
+        for (size_t k = 0; k < cg->lane_state.size(); ++k)
+            std::fill(limg.begin() + k * per, limg.begin() + (k + 1) * per, cg->lane_state[k].init(e));
+        bounce.h2d(d_lane_state, limg.data(), limg.size() * 4, stream);
+    }
+    if (d_bus_phase) HIPCK(hipMemsetAsync(d_bus_phase, 0, 4, stream));
+    conv_reset();
+    // prepare(): every Delay gets a fresh zeroed ring sized from the sample rate (delay/mod.rs:59-69)
+    for (size_t k = 0; k < cg->rings.size(); ++k) {
+        const uint32_t cap = cg->rings[k].capacity(sr);
+        if (cap != ring_cap[k]) {
+            if (d_ring[k]) HIPCK(hipFree(d_ring[k]));
+            d_ring[k] = nullptr;
+            ring_cap[k] = 0;
+            HIPCK(hipMalloc(&d_ring[k], (size_t)cap * V * 4));
+            ring_cap[k] = cap;
         }
+        HIPCK(hipMemsetAsync(d_ring[k], 0, (size_t)cap * V * 4, stream));
+    }
+    HIPCK(hipStreamSynchronize(stream));
+}
+
+// ---- event timeline: the device halves of og_timeline.h's two update paths ---------------------------------------------
+void og_engine::full_rebuild()
+{
+    HostProf::Scope ps(prof, HostProf::REBUILD);
+    EventTimeline::Rebuild r = tl.plan_rebuild(consumed_horizon(), d_events != nullptr);
+    const size_t n = r.events.size();
+    if (r.realloc) {
+        if (d_events) HIPCK(hipFree(d_events));
+        d_events = nullptr;
+        if (!r.capacity) throw ogabi::Error(OG_E_NOMEM, "event timeline + og_reserve_events exceed the 32-bit event ring");
+        HIPCK(hipMalloc(&d_events, r.capacity * sizeof(OgEvent)));
+    }
+    if (n) bounce.h2d(d_events, r.events.data(), n * sizeof(OgEvent), stream);
+    bounce.h2d(d_ev_cursor, r.cursor.data(), (size_t)V * 4, stream);
+    bounce.h2d(d_ev_end, r.end.data(), (size_t)V * 4, stream);
+    HIPCK(hipStreamSynchronize(stream)); // the staging vectors die here
+    tl.adopt(r);
+}
+
+bool og_engine::incremental_update()
+{
+    HostProf::Scope ps(prof, HostProf::INCREMENTAL);
+    if (!h_stage_ev[0]) {
         for (int i = 0; i < EV_RING; ++i) {
-            if (h_stage_ev[i]) (void)hipHostFree(h_stage_ev[i]);
-            if (h_stage_upd[i]) (void)hipHostFree(h_stage_upd[i]);
-            (void)hipFree(d_stage_upd[i]);
+            HIPCK(hipHostMalloc((void**)&h_stage_ev[i], tl.stage_events() * sizeof(OgEvent), hipHostMallocDefault));
+            HIPCK(hipHostMalloc((void**)&h_stage_upd[i], tl.stage_events() * EV_UPD_WORDS * 4, hipHostMallocDefault));
         }
-        if (h_progress) (void)hipHostFree((void*)h_progress);
-        if (h_bus_pinned) (void)hipHostFree(h_bus_pinned);
-        if (h_clock) (void)hipHostFree(h_clock);
-        for (auto ev : t_start) (void)hipEventDestroy(ev);
-        for (auto ev : t_stop) (void)hipEventDestroy(ev);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
+    const int r = stage_head;
+    {
+        HostProf::Scope pw(prof, HostProf::EV_WAIT);
+        batch_done(stage_seq[r]); // (EV_RING batches ago: long done)
+    }
+    TlEvent* sev = h_stage_ev[r];
+    uint32_t* upd = h_stage_upd[r];
+    const EventTimeline::Batch b = tl.plan_incremental(sev, upd, consumed_horizon(), launch_end());
+    if (!b) return false;
+    if (b.n_upd == 0) return true; // (every due entry was stale, nothing was pushed: no kernel to launch)
+    // commit: host mirror, then the device
+    HostProf::Scope pc(prof, HostProf::EV_COMMIT);
+    tl.commit_incremental(b, sev, upd);
+    static_assert(sizeof(OgEvent) == sizeof(uint4), "og_apply_event_updates copies events as 16-byte words");
+    const uint32_t n_wg_upd = (uint32_t)((std::max(b.n_upd, b.n_ev) + 255) / 256);
+    hipLaunchKernelGGL(og_apply_event_updates, dim3(n_wg_upd), dim3(256), 0, stream, (const uint4*)sev, (uint32_t)b.n_ev,
+                       (uint4*)(d_events + b.base), (const uint32_t*)upd, (uint32_t)b.n_upd, d_ev_cursor, d_ev_end);
+    HIPCK(hipGetLastError());
+    stage_seq[r] = flush_seq + 1; // read in stream order before the batch that is about to be launched
+    batch_staged = true;
+    stage_head = (stage_head + 1) % EV_RING;
+    return true;
+}
 
-    ogc::UEnv env() const { return ogc::UEnv{sr, values.data()}; }
+void og_engine::upload_events()
+{
+    if (!tl.needs_upload(launch_end())) return;
+    EventTimeline::HoldLocal hold(tl); // (block-local pushes of the block being assembled stay on the host)
+    if (!tl.needs_upload(launch_end())) return;
+    HostProf::Scope ps(prof, HostProf::SYNC_EVENTS);
+    // many voices touched at once (bulk scheduling): one compact CSR rebuild beats per-voice segments
+    const bool bulk = tl.wants_rebuild() || tl.n_pending() > tl.stage_events() || tl.n_pending() > (size_t)V / 2 + 64 || !d_events;
+    if (bulk || !incremental_update()) full_rebuild();
+}
 
-    void upload_initial_state()
-    {
-        const size_t nw = cg->state.size();
-        std::vector<uint32_t> img(nw * (size_t)V);
-        ogc::UEnv e = env();
-        for (size_t w = 0; w < nw; ++w) {
-            const uint32_t bits = cg->state[w].init(e);
-            std::fill(img.begin() + w * V, img.begin() + (w + 1) * V, bits);
-        }
-        bounce.h2d(d_state, img.data(), img.size() * 4, stream);
-        std::vector<uint32_t> limg;
-        if (!cg->lane_state.empty()) {
-            const size_t per = (size_t)V * cg->lpv * cg->lane_width;
-            limg.resize(cg->lane_state.size() * per);
-            for (size_t k = 0; k < cg->lane_state.size(); ++k)
-                std::fill(limg.begin() + k * per, limg.begin() + (k + 1) * per, cg->lane_state[k].init(e));
-            bounce.h2d(d_lane_state, limg.data(), limg.size() * 4, stream);
-        }
-        if (d_bus_phase) HIPCK(hipMemsetAsync(d_bus_phase, 0, 4, stream));
-        conv_reset();
-        // prepare(): every Delay gets a fresh zeroed ring sized from the sample rate (delay/mod.rs:59-69)
-        for (size_t k = 0; k < cg->rings.size(); ++k) {
-            const uint32_t cap = cg->rings[k].capacity(sr);
-            if (cap != ring_cap[k]) {
-                if (d_ring[k]) HIPCK(hipFree(d_ring[k]));
-                d_ring[k] = nullptr;
-                ring_cap[k] = 0;
-                HIPCK(hipMalloc(&d_ring[k], (size_t)cap * V * 4));
-                ring_cap[k] = cap;
-            }
-            HIPCK(hipMemsetAsync(d_ring[k], 0, (size_t)cap * V * 4, stream));
-        }
-        HIPCK(hipStreamSynchronize(stream));
-    }
-    size_t ring_bytes() const
-    {
-        size_t n = 0;
-        for (size_t k = 0; k < cg->rings.size(); ++k) n += (size_t)ring_cap[k] * V * 4;
-        return n;
-    }
+bool og_engine::rcp_cover(uint32_t need)
+{
+    if (need > rcp_cap) return false;
+    if (need <= rcp_n) return true;
+    const uint32_t n = std::min(rcp_cap, std::max(need, 2 * rcp_n));
+    float* t = nullptr;
+    HIPCK(hipMalloc(&t, ((size_t)OG_RCP_PAD + n + 1) * sizeof(float)));
+    const uint32_t words = OG_RCP_PAD + n + 1;
+    hipLaunchKernelGGL(og::rcp_table_fill<0>, dim3((words + 255) / 256), dim3(256), 0, stream, t, n);
+    HIPCK(hipGetLastError());
+    if (d_rcp) rcp_old.push_back(d_rcp);
+    d_rcp = t;
+    rcp_n = n;
+    return true;
+}
 
-    void reset_timeline()
-    {
-        pending.clear();
-        local_from = 0;
-        h_events.clear();
-        seg_begin.clear();
-        seg_end.clear();
-        seg_last.clear();
-        cont_begin.clear();
-        cont_end.clear();
-        cont_last.clear();
-        cont_due.clear();
-        n_conts = 0;
-        ev_tail = 0;
-        ring_live.clear();
-        ev_rebuild = false;
-        n_block_local = 0;
-        clear_local_counts();
-        HIPCK(hipMemsetAsync(d_ev_cursor, 0, (size_t)V * 4, stream));
-        HIPCK(hipMemsetAsync(d_ev_end, 0, (size_t)V * 4, stream));
+void og_engine::alloc_bus_buffers(uint32_t batch)
+{
+    HIPCK(hipStreamSynchronize(stream));
+    for (float** p : {&d_partials, &d_partials2, &d_mono, &d_stage_bus})
+        if (*p) {
+            HIPCK(hipFree(*p));
+            *p = nullptr;
+        }
+    batch_cap = batch;
+    const size_t max_frames = (size_t)OG_MAX_BLOCK * batch;
+    const size_t vc = cg->voice_channels; // a Frame<2> voice output: two planes of partial rows
+    HIPCK(hipMalloc(&d_partials, (size_t)n_wg * max_frames * 4 * vc));
+    HIPCK(hipMemset(d_partials, 0, (size_t)n_wg * max_frames * 4 * vc));
+    HIPCK(hipMalloc(&d_partials2, ((size_t)n_wg / OG_RED_GROUP + 2 + 64) * max_frames * 4));
+    HIPCK(hipMalloc(&d_stage_bus, max_frames * OG_MAX_BUS_CHANNELS * 4));
+    if (cg->bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
+    if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(std::max(conv.cur ? conv.cur->K() : 0u, conv.old ? conv.old->K() : 0u));
+    const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
+    for (int i = 0; i < RAMP_RING && rows; ++i) {
+        if (d_ramp[i]) HIPCK(hipFree(d_ramp[i]));
+        if (h_ramp[i]) HIPCK(hipHostFree(h_ramp[i]));
+        d_ramp[i] = h_ramp[i] = nullptr;
+        HIPCK(hipMalloc(&d_ramp[i], rows * max_frames * 4));
+        HIPCK(hipHostMalloc((void**)&h_ramp[i], rows * max_frames * 4, hipHostMallocDefault));
+        ramp_seq[i] = 0;
     }
+}
 
-    void clear_local_counts()
-    {
-        for (uint32_t k : local_touched) local_cnt[k] = 0;
-        local_touched.clear();
-    }
-
-    // Everything before this frame has been consumed on the device by the time an update issued now takes effect:
-    // launched blocks run before it in stream order; blocks still in the queue have not seen their events yet.
-    // Blocks per launch for throughput callers (og_render*, cluster shards, og_set_bus_batching(e, 0)): as many as the
-    // launch overhead still pays for while the launch's partial-sum rows stay modest.  Measured: fm_voice at 65 536 voices
-    // gains 30 % from 1 -> 8 blocks and 3.5 % more from 8 -> 32 (32 MB of rows); sat4x_voice at 131 072 voices and sub_voice
-    // at 262 144 LOSE 10-25 % once the rows of one launch pass ~64 MB, with either row layout (not understood further).
-    uint32_t auto_batch() const
-    {
-        const size_t per_block = (size_t)std::max<uint32_t>(n_wg, 1u) * 256u * 4u; // rows of one 256-frame block
-        const size_t b = ((size_t)32 << 20) / per_block;
-        return (uint32_t)std::min<size_t>(OG_MAX_LAUNCH_BLOCKS, std::max<size_t>(8, b));
-    }
-    uint64_t consumed_horizon() const { return queue.empty() ? frame_now : q_frame0; }
-    // unconsumed events of voice v on the device timeline (a block consumes everything before its end)
-    bool has_old_events(uint32_t v) const
-    {
-        if (seg_begin.empty()) return false;
-        const uint64_t hz = consumed_horizon();
-        return (seg_begin[v] != seg_end[v] && seg_last[v] >= hz) || (has_cont(v) && cont_last[v] >= hz);
-    }
-    void old_events(uint32_t v, std::vector<OgEvent>& out, uint64_t hz) const
-    {
-        uint32_t hb, he, cb, ce;
-        unconsumed_ranges(v, hz, hb, he, cb, ce); // (binary search for the horizon: no walk over what has been played)
-        out.insert(out.end(), h_events.begin() + hb, h_events.begin() + he);
-        out.insert(out.end(), h_events.begin() + cb, h_events.begin() + ce);
-    }
-    void old_events(uint32_t v, std::vector<OgEvent>& out) const
-    {
-        if (!has_old_events(v)) return; // (no look at h_events: cold memory)
-        old_events(v, out, consumed_horizon());
-    }
-
-    static bool push_order(const HostEvent& a, const HostEvent& b)
-    {
-        if (a.voice != b.voice) return a.voice < b.voice;
-        if (a.frame != b.frame) return a.frame < b.frame;
-        return a.seq < b.seq;
-    }
-
-    // old (already on the device) before new on equal frames: the old ones were pushed earlier
-    static void merge_by_frame(const std::vector<OgEvent>& old, const HostEvent* nb, const HostEvent* ne,
-                               std::vector<OgEvent>& out)
-    {
-        size_t i = 0;
-        while (i < old.size() || nb != ne) {
-            if (nb == ne || (i < old.size() && old[i].frame <= nb->frame)) {
-                out.push_back(old[i++]);
-            } else {
-                out.push_back(OgEvent{nb->frame, nb->target, nb->value});
-                ++nb;
-            }
-        }
-    }
-
-    void full_rebuild()
-    {
-        HostProf::Scope ps(prof, HostProf::REBUILD);
-        std::stable_sort(pending.begin(), pending.end(), push_order);
-        std::vector<OgEvent> evs;
-        std::vector<uint32_t> cursor(V), end(V);
-        std::vector<uint64_t> last(V, 0);
-        std::vector<OgEvent> old;
-        size_t p = 0;
-        const size_t np = pending.size();
-        const bool had = !seg_begin.empty();
-        evs.reserve(np + (had ? ev_tail : 0));
-        for (uint32_t v = 0; v < V; ++v) {
-            cursor[v] = (uint32_t)evs.size();
-            size_t q = p;
-            while (q < np && pending[q].voice == v) ++q;
-            if (had && (seg_begin[v] != seg_end[v] || has_cont(v))) {
-                old.clear();
-                old_events(v, old);
-                merge_by_frame(old, pending.data() + p, pending.data() + q, evs);
-            } else {
-                for (size_t i = p; i < q; ++i) evs.push_back(OgEvent{pending[i].frame, pending[i].target, pending[i].value});
-            }
-            p = q;
-            end[v] = (uint32_t)evs.size();
-            if (end[v] != cursor[v]) last[v] = evs.back().frame;
-        }
-        const size_t n = evs.size();
-        if (n > 0xFFFFFFF0ull) throw std::runtime_error("event timeline too long");
-        if (n + std::max<size_t>(std::min<size_t>(EV_STAGE_EVENTS, 64), ev_reserve) > ev_cap || !d_events) {
-            if (d_events) HIPCK(hipFree(d_events));
-            d_events = nullptr;
-            size_t headroom = (size_t)2 << 20; // room for appended segments (2 M events, 32 MB) before the ring has to wrap
-            if (ev_headroom_env) headroom = ev_headroom_env; // OSCEN_GPU_EV_HEADROOM (tests: force compactions), read at og_create
-            ev_cap = std::max<size_t>(n + std::max<size_t>(n / 2, ev_reserve), 1024) + headroom;
-            // ring positions (seg_begin / seg_end, the device cursor and end words) are 32-bit: the ring never grows past
-            // what they address -- the slack shrinks first, and a score that does not fit with its reserve is refused
-            const size_t EV_CAP_MAX = 0xFFFFFFF0ull;
-            if (ev_cap > EV_CAP_MAX) ev_cap = EV_CAP_MAX;
-            if (n + ev_reserve > ev_cap) throw ogabi::Error(OG_E_NOMEM, "event timeline + og_reserve_events exceed the 32-bit event ring");
-            HIPCK(hipMalloc(&d_events, ev_cap * sizeof(OgEvent)));
-        }
-        if (n) bounce.h2d(d_events, evs.data(), n * sizeof(OgEvent), stream);
-        bounce.h2d(d_ev_cursor, cursor.data(), (size_t)V * 4, stream);
-        bounce.h2d(d_ev_end, end.data(), (size_t)V * 4, stream);
-        cont_due.clear();
-        HIPCK(hipStreamSynchronize(stream)); // the staging vectors die here
-        h_events.swap(evs);
-        // mirror of the whole ring, reserved up front so that the live path never reallocates while playing (grown on demand:
-        // no zero-fill of the room here) -- up to 2^28 events (4 GB of host memory); a ring larger than that mirrors what is
-        // resident plus the promised reserve and grows on demand beyond it
-        h_events.reserve(ev_cap <= ((size_t)1 << 28) ? ev_cap : std::min(ev_cap, h_events.size() + std::max<size_t>(ev_reserve, (size_t)1 << 28)));
-        // ... and the first half gigabyte of that room is touched HERE, while the score is being laid out: the live path appends
-        // ~150 KB of segments per block at 8 M voices, i.e. it enters a fresh 2 MB region of this mapping every dozen blocks,
-        // and a first touch that has to wait for the kernel to find (compact) a huge page is a stall of milliseconds on the
-        // real-time path (one 12.5 ms block in five driver-command runs of round 6, one 6.4 ms block in round 5's -- neither
-        // reproduced on demand).  Half a gigabyte covers ~3 000 blocks of live playing at that size; costs ~0.1 s here.
-        {
-            const size_t room = (h_events.capacity() - h_events.size()) * sizeof(OgEvent);
-            if (room) memset(reinterpret_cast<char*>(h_events.data()) + h_events.size() * sizeof(OgEvent), 0, std::min<size_t>(room, (size_t)512 << 20));
-        }
-        seg_begin.swap(cursor);
-        seg_end.swap(end);
-        seg_last.swap(last);
-        n_conts = 0;
-        cont_begin.assign(V, 0); // (everything is in the segments now; the arrays are sized here, not on the live path)
-        cont_end.assign(V, 0);
-        cont_last.assign(V, 0);
-        ev_tail = n;
-        ring_live.clear();
-        for (uint32_t v = 0; v < V; ++v)
-            if (seg_begin[v] != seg_end[v]) ring_live.push_back(RingSeg{v, seg_begin[v], seg_end[v]});
-        pending.clear();
-        local_from = 0;
-        ev_rebuild = false;
-        n_full_rebuilds += 1;
-    }
-
-    // One voice of an incremental batch: its pushes `mine` (sorted; may be empty: a voice whose continuation falls due) merged
-    // with what it still has to play UP TO `bound` = the later of the last pushed frame and the end of the launch being
-    // prepared; what lies behind stays where it is and becomes (or remains) the continuation -- the rest of a long score is
-    // never copied.  A short rest is carried over instead.  A voice without pushes whose segment has been played is simply
-    // pointed at its continuation: no record is written at all.  false: the batch does not fit the staging buffer.
-    bool merge_voice(uint32_t v, const std::vector<HostEvent>& mine, uint64_t lend, OgEvent* sev, uint32_t* upd, size_t& n_ev, size_t& n_upd,
-                     std::vector<uint32_t>& kept, std::vector<OgEvent>& old, std::vector<OgEvent>& merged)
-    {
-        old.clear();
-        merged.clear();
-        uint32_t keep_b = 0, keep_e = 0;
-        if (!mine.empty() && !has_cont(v) && seg_end[v] - seg_begin[v] < CONT_MIN) {
-            // the usual loaded voice: a handful of waiting events, no continuation, nothing worth leaving behind -- one pass
-            // over the segment, as before round 6 (the real-time banks: ~1000 of these per block)
-            const uint64_t hz = consumed_horizon();
-            if (seg_last[v] >= hz)
-                for (uint32_t i = seg_begin[v]; i < seg_end[v]; ++i)
-                    if (h_events[i].frame >= hz) old.push_back(h_events[i]);
-            merge_by_frame(old, mine.data(), mine.data() + mine.size(), merged);
-            if (n_ev + merged.size() > EV_STAGE_EVENTS || n_upd >= EV_STAGE_EVENTS) return false;
-            memcpy(sev + n_ev, merged.data(), merged.size() * sizeof(OgEvent));
-            upd[EV_UPD_WORDS * n_upd] = v;
-            upd[EV_UPD_WORDS * n_upd + 1] = (uint32_t)n_ev;
-            upd[EV_UPD_WORDS * n_upd + 2] = (uint32_t)(n_ev + merged.size());
-            n_ev += merged.size();
-            n_upd += 1;
-            return true;
-        }
-        const uint64_t bound = std::max<uint64_t>(mine.empty() ? 0 : mine.back().frame, lend ? lend - 1 : 0);
-        uint32_t hb, he, cb, ce;
-        unconsumed_ranges(v, consumed_horizon(), hb, he, cb, ce);
-        if (mine.empty()) {
-            if (cb == ce) return true; // (nothing left behind after all)
-            if (hb == he) { // the segment in front has been played: the continuation IS the voice's segment from here on
-                if (n_upd >= EV_STAGE_EVENTS) return false;
-                upd[EV_UPD_WORDS * n_upd] = v;
-                upd[EV_UPD_WORDS * n_upd + 1] = cb; // (absolute ring positions)
-                upd[EV_UPD_WORDS * n_upd + 2] = ce;
-                kept.insert(kept.end(), {(uint32_t)n_upd, 0u, 0u, 1u});
-                n_upd += 1;
-                return true;
-            }
-        }
-        if (cb != ce) { // (every frame of the segment is <= every frame of the continuation)
-            const uint32_t split = upper_frame(cb, ce, bound);
-            old.insert(old.end(), h_events.begin() + hb, h_events.begin() + he);
-            old.insert(old.end(), h_events.begin() + cb, h_events.begin() + split);
-            if (ce - split >= CONT_MIN) {
-                keep_b = split;
-                keep_e = ce;
-            } else {
-                old.insert(old.end(), h_events.begin() + split, h_events.begin() + ce);
-            }
-        } else {
-            const uint32_t split = upper_frame(hb, he, bound);
-            if (he - split >= CONT_MIN) {
-                old.insert(old.end(), h_events.begin() + hb, h_events.begin() + split);
-                keep_b = split;
-                keep_e = he;
-            } else {
-                old.insert(old.end(), h_events.begin() + hb, h_events.begin() + he);
-            }
-        }
-        merge_by_frame(old, mine.data(), mine.data() + mine.size(), merged);
-        if (merged.empty()) { // (only a rest behind the launch: point the voice at it, as above)
-            if (keep_b == keep_e) return true;
-            if (n_upd >= EV_STAGE_EVENTS) return false;
-            upd[EV_UPD_WORDS * n_upd] = v;
-            upd[EV_UPD_WORDS * n_upd + 1] = keep_b;
-            upd[EV_UPD_WORDS * n_upd + 2] = keep_e;
-            kept.insert(kept.end(), {(uint32_t)n_upd, 0u, 0u, 1u});
-            n_upd += 1;
-            return true;
-        }
-        if (n_ev + merged.size() > EV_STAGE_EVENTS || n_upd >= EV_STAGE_EVENTS) return false;
-        memcpy(sev + n_ev, merged.data(), merged.size() * sizeof(OgEvent));
-        upd[EV_UPD_WORDS * n_upd] = v;
-        upd[EV_UPD_WORDS * n_upd + 1] = (uint32_t)n_ev; // (relative to the batch: its place in the ring is chosen at the commit)
-        upd[EV_UPD_WORDS * n_upd + 2] = (uint32_t)(n_ev + merged.size());
-        if (keep_b != keep_e) kept.insert(kept.end(), {(uint32_t)n_upd, keep_b, keep_e, 0u});
-        n_ev += merged.size();
-        n_upd += 1;
-        return true;
-    }
-
-    // live pushes: O(#pushes) host work, asynchronous upload.  Returns false when the batch does not fit
-    // (staging buffer, tail of d_events): the caller falls back to full_rebuild().
-    bool incremental_update()
-    {
-        HostProf::Scope ps(prof, HostProf::INCREMENTAL);
-        if (pending.size() > EV_STAGE_EVENTS) return false;
-        if (!h_stage_ev[0]) {
-            for (int i = 0; i < EV_RING; ++i) {
-                HIPCK(hipHostMalloc((void**)&h_stage_ev[i], EV_STAGE_EVENTS * sizeof(OgEvent), hipHostMallocDefault));
-                HIPCK(hipHostMalloc((void**)&h_stage_upd[i], EV_STAGE_EVENTS * EV_UPD_WORDS * 4, hipHostMallocDefault));
-            }
-        }
-        if (seg_begin.empty()) {
-            seg_begin.assign(V, 0);
-            seg_end.assign(V, 0);
-            seg_last.assign(V, 0);
-            ensure_cont();
-        }
-        // group the pending pushes per voice without sorting the batch: chain them in arrival order (O(n)), then put
-        // every (short) chain into (frame, push order)
-        const size_t np = pending.size();
-        constexpr uint32_t NONE = 0xFFFFFFFFu;
-        if (grp_head.empty()) {
-            grp_head.assign(V, NONE);
-            grp_tail.assign(V, NONE);
-        }
-        grp_next.assign(np, NONE);
-        grp_voices.clear();
-        for (size_t i = 0; i < np; ++i) {
-            const uint32_t v = pending[i].voice;
-            if (grp_head[v] == NONE) {
-                grp_head[v] = (uint32_t)i;
-                grp_voices.push_back(v);
-            } else {
-                grp_next[grp_tail[v]] = (uint32_t)i;
-            }
-            grp_tail[v] = (uint32_t)i;
-        }
-        // voices whose continuation has its first event inside the launch being prepared (and no push in this batch: a
-        // pushed voice is brought up to the end of the launch anyway)
-        const uint64_t lend = launch_end();
-        std::vector<uint32_t> due;
-        while (!cont_due.empty() && cont_due.front().first < lend) {
-            const std::pair<uint64_t, uint32_t> top = cont_due.front();
-            std::pop_heap(cont_due.begin(), cont_due.end(), std::greater<std::pair<uint64_t, uint32_t>>());
-            cont_due.pop_back();
-            const uint32_t v = top.second;
-            if (!has_cont(v) || h_events[cont_begin[v]].frame != top.first) continue; // (stale: the voice was merged or re-pointed since)
-            if (grp_head[v] != NONE) continue;
-            due.push_back(v);
-        }
-        std::sort(due.begin(), due.end());
-        due.erase(std::unique(due.begin(), due.end()), due.end());
-        const int r = stage_head;
-        {
-            HostProf::Scope pw(prof, HostProf::EV_WAIT);
-            batch_done(stage_seq[r]); // (EV_RING batches ago: long done)
-        }
-        OgEvent* sev = h_stage_ev[r];
-        uint32_t* upd = h_stage_upd[r];
-        std::vector<OgEvent> old, merged;
-        std::vector<HostEvent> mine;
-        // the updates that are not plain "new segment, no continuation" (few): {update index, begin and end of the continuation
-        // the voice keeps, 1 = the update's positions are absolute ring positions (the voice is pointed at records in place)}
-        std::vector<uint32_t> kept;
-        size_t n_ev = 0, n_upd = 0;
-        bool fits = true;
-        for (const uint32_t v : grp_voices) {
-            // the usual live case: nothing of this voice is waiting on the device and its pushes arrived in frame order
-            // (a note-on is a frequency value and a gate on one frame) -- straight into the staging buffer
-            if (fits && !has_old_events(v)) {
-                size_t k = 0;
-                uint64_t last = 0;
-                bool ordered = true;
-                for (uint32_t i = grp_head[v]; i != NONE; i = grp_next[i], ++k) {
-                    const HostEvent& h = pending[i];
-                    ordered = ordered && h.frame >= last;
-                    last = h.frame;
-                    if (n_ev + k < EV_STAGE_EVENTS) sev[n_ev + k] = OgEvent{h.frame, h.target, h.value};
-                }
-                if (ordered && n_ev + k <= EV_STAGE_EVENTS) {
-                    grp_head[v] = NONE;
-                    upd[EV_UPD_WORDS * n_upd] = v; // (cursor, end) relative to the batch: its place in the ring is chosen below
-                    upd[EV_UPD_WORDS * n_upd + 1] = (uint32_t)n_ev;
-                    upd[EV_UPD_WORDS * n_upd + 2] = (uint32_t)(n_ev + k);
-                    n_ev += k;
-                    n_upd += 1;
-                    continue;
-                }
-            }
-            mine.clear();
-            for (uint32_t i = grp_head[v]; i != NONE; i = grp_next[i]) mine.push_back(pending[i]);
-            grp_head[v] = NONE; // (left clean for the next batch, also on the early exit below)
-            if (!fits) continue;
-            for (size_t i = 1; i < mine.size(); ++i) { // insertion sort by frame; arrival order breaks ties
-                const HostEvent k = mine[i];
-                size_t j = i;
-                while (j > 0 && mine[j - 1].frame > k.frame) {
-                    mine[j] = mine[j - 1];
-                    --j;
-                }
-                mine[j] = k;
-            }
-            if (!merge_voice(v, mine, lend, sev, upd, n_ev, n_upd, kept, old, merged)) fits = false;
-        }
-        for (const uint32_t v : due) { // (after the pushed voices: `due` holds none of them)
-            if (!fits) { // (the batch goes to full_rebuild, which merges every continuation)
-                break;
-            }
-            mine.clear();
-            if (!merge_voice(v, mine, lend, sev, upd, n_ev, n_upd, kept, old, merged)) fits = false;
-        }
-        if (!fits) return false;
-        if (n_upd == 0) { // (every due entry was stale, nothing was pushed: no kernel to launch)
-            pending.clear();
-            local_from = 0;
-            return true;
-        }
-        // a place in the ring for the whole batch (the segments touched above count as superseded only after the commit,
-        // so the batch never lands on the old events it was merged from)
-        const size_t base = ring_alloc(n_ev);
-        if (base == SIZE_MAX) return false;
-        // commit: host mirror, then the device
-        HostProf::Scope pc(prof, HostProf::EV_COMMIT);
-        if (h_events.size() < base + n_ev) h_events.resize(base + n_ev); // (capacity ev_cap is reserved: no reallocation, no fill of the unused room)
-        memcpy(h_events.data() + base, sev, n_ev * sizeof(OgEvent));
-        size_t kq = 0; // (next entry of `kept`: they are in update order)
-        for (size_t i = 0; i < n_upd; ++i) {
-            uint32_t* u = upd + EV_UPD_WORDS * i;
-            const uint32_t v = u[0];
-            uint32_t kb = 0, ke = 0, in_place = 0;
-            if (kq < kept.size() && kept[kq] == (uint32_t)i) {
-                kb = kept[kq + 1];
-                ke = kept[kq + 2];
-                in_place = kept[kq + 3];
-                kq += 4;
-            }
-            if (in_place) { // pointed at records that are in the ring already (the segment they lie in stays alive: ring_alloc)
-                seg_begin[v] = u[1];
-                seg_end[v] = u[2];
-                seg_last[v] = h_events[u[2] - 1].frame;
-                if (n_conts) set_cont(v, 0u, 0u);
-                continue;
-            }
-            seg_last[v] = sev[u[2] - 1].frame;
-            u[1] += (uint32_t)base;
-            u[2] += (uint32_t)base;
-            seg_begin[v] = u[1];
-            seg_end[v] = u[2];
-            if (kb != ke) {
-                ensure_cont();
-                set_cont(v, kb, ke);
-                cont_due_push(v);
-            } else if (n_conts) {
-                set_cont(v, 0u, 0u);
-            }
-            ring_live.push_back(RingSeg{v, u[1], u[2]});
-        }
-        n_events_copied += n_ev;
-        ev_tail = base;
-        static_assert(sizeof(OgEvent) == sizeof(uint4), "og_apply_event_updates copies events as 16-byte words");
-        const uint32_t n_wg_upd = (uint32_t)((std::max(n_upd, n_ev) + 255) / 256);
-        hipLaunchKernelGGL(og_apply_event_updates, dim3(n_wg_upd), dim3(256), 0, stream, (const uint4*)sev, (uint32_t)n_ev,
-                           (uint4*)(d_events + ev_tail), (const uint32_t*)upd, (uint32_t)n_upd, d_ev_cursor, d_ev_end);
-        HIPCK(hipGetLastError());
-        stage_seq[r] = flush_seq + 1; // read in stream order before the batch that is about to be launched
-        batch_staged = true;
-        stage_head = (stage_head + 1) % EV_RING;
-        ev_tail += n_ev;
-        pending.clear();
-        local_from = 0;
-        n_incremental += 1;
-        return true;
-    }
-
-    // a block of `frames` frames is about to be queued: a try_push'ed event whose frame_offset >= frames is never
-    // delivered (the reference clears the queues at the end of the block)
-    void drop_late_local(uint32_t frames)
-    {
-        const size_t from = std::min(local_from, pending.size()); // pushes since the previous block sit behind this index
-        local_from = pending.size();
-        if (!n_block_local) return;
-        const uint64_t lim = frame_now + frames;
-        const size_t before = pending.size();
-        pending.erase(std::remove_if(pending.begin() + (long)from, pending.end(),
-                                     [&](const HostEvent& h) { return h.block_local && h.frame >= lim; }),
-                      pending.end());
-        dropped += before - pending.size();
-        for (size_t i = from; i < pending.size(); ++i) pending[i].block_local = false; // (delivered: part of the timeline from here on)
-        local_from = pending.size();
-        n_block_local = 0;
-        clear_local_counts();
-    }
-    // bring the device timeline up to date: right before the queued blocks are launched (their events may have arrived
-    // over several blocks: one staging copy and one cursor update for all of them)
-    void upload_events()
-    {
-        if (pending.empty() && !ev_rebuild && !continuation_due()) return;
-        // try_push'ed events of the block that is still being assembled (pushed since the last block was queued) stay
-        // on the host: drop_late_local() has not judged them against that block's length yet.  A flush in between --
-        // og_process_block launches earlier async blocks, the setters launch the queue -- must not turn an event whose
-        // frame_offset >= frames into one that fires in a later block.
-        std::vector<HostEvent> held;
-        if (n_block_local > 0) {
-            const size_t from = std::min(local_from, pending.size());
-            auto mid = std::stable_partition(pending.begin() + (long)from, pending.end(), [](const HostEvent& h) { return !h.block_local; });
-            held.assign(mid, pending.end());
-            pending.erase(mid, pending.end());
-        }
-        struct PutBack {
-            og_engine* e;
-            std::vector<HostEvent>& held;
-            ~PutBack()
-            {
-                if (held.empty()) return;
-                e->local_from = std::min(e->local_from, e->pending.size());
-                e->pending.insert(e->pending.end(), held.begin(), held.end());
-            }
-        } put_back{this, held};
-        if (pending.empty() && !ev_rebuild && !continuation_due()) return;
-        HostProf::Scope ps(prof, HostProf::SYNC_EVENTS);
-        // many voices touched at once (bulk scheduling): one compact CSR rebuild beats per-voice segments
-        const bool bulk = ev_rebuild || pending.size() > EV_STAGE_EVENTS || pending.size() > (size_t)V / 2 + 64 || !d_events;
-        if (bulk || !incremental_update()) full_rebuild();
-    }
-
-    // the longest release, in samples, of the outer-rate envelopes under these block-uniform slots
-    uint32_t release_need(const uint32_t* slots) const
-    {
-        uint32_t need = 0;
-        for (int k : cg->release_slots) need = std::max(need, slots[k]);
-        return need;
-    }
-    // make the reciprocal table cover `need` entries (stream-ordered: the fill runs ahead of the launches that read it);
-    // false when `need` is over the cap
-    bool rcp_cover(uint32_t need)
-    {
-        if (need > rcp_cap) return false;
-        if (need <= rcp_n) return true;
-        const uint32_t n = std::min(rcp_cap, std::max(need, 2 * rcp_n));
-        float* t = nullptr;
-        HIPCK(hipMalloc(&t, ((size_t)OG_RCP_PAD + n + 1) * sizeof(float)));
-        const uint32_t words = OG_RCP_PAD + n + 1;
-        hipLaunchKernelGGL(og::rcp_table_fill<0>, dim3((words + 255) / 256), dim3(256), 0, stream, t, n);
-        HIPCK(hipGetLastError());
-        if (d_rcp) rcp_old.push_back(d_rcp);
-        d_rcp = t;
-        rcp_n = n;
-        return true;
-    }
-
-    void alloc_bus_buffers(uint32_t batch)
-    {
-        HIPCK(hipStreamSynchronize(stream));
-        for (float** p : {&d_partials, &d_partials2, &d_mono, &d_stage_bus})
-            if (*p) {
-                HIPCK(hipFree(*p));
-                *p = nullptr;
-            }
-        batch_cap = batch;
-        const size_t max_frames = (size_t)OG_MAX_BLOCK * batch;
-        const size_t vc = cg->voice_channels; // a Frame<2> voice output: two planes of partial rows
-        HIPCK(hipMalloc(&d_partials, (size_t)n_wg * max_frames * 4 * vc));
-        HIPCK(hipMemset(d_partials, 0, (size_t)n_wg * max_frames * 4 * vc));
-        HIPCK(hipMalloc(&d_partials2, ((size_t)n_wg / OG_RED_GROUP + 2 + 64) * max_frames * 4));
-        HIPCK(hipMalloc(&d_stage_bus, max_frames * OG_MAX_BUS_CHANNELS * 4));
-        if (cg->bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
-        if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(std::max(conv.cur ? conv.cur->K() : 0u, conv.old ? conv.old->K() : 0u));
-        const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
-        for (int i = 0; i < RAMP_RING && rows; ++i) {
-            if (d_ramp[i]) HIPCK(hipFree(d_ramp[i]));
-            if (h_ramp[i]) HIPCK(hipHostFree(h_ramp[i]));
-            d_ramp[i] = h_ramp[i] = nullptr;
-            HIPCK(hipMalloc(&d_ramp[i], rows * max_frames * 4));
-            HIPCK(hipHostMalloc((void**)&h_ramp[i], rows * max_frames * 4, hipHostMallocDefault));
-            ramp_seq[i] = 0;
-        }
-    }
-
-    // process_block(frames), asynchronous: the block joins the queue; the queue is launched when it is full or when
-    // something needs its results or is about to change what it would see
-    void process_async(uint32_t frames, float* d_out)
-    {
-        HIPCK(hipSetDevice(device));
-        drop_late_local(frames);
-        // events wait on the host until the queue is launched: launch it before they outgrow the staging buffers (or the
-        // size up to which per-voice segments beat a rebuild of the whole timeline)
-        if (!queue.empty() && pending.size() > std::min<size_t>(EV_STAGE_EVENTS / 2, (size_t)V / 4 + 32)) flush_bus();
-        if (queue.empty()) {
-            q_frame0 = frame_now;
-            q_frames = 0;
-            q_ramps = cg->n_streams > 0;
-            q_ramp_slot = -1;
-        }
-        // tick_ramps (codegen/mod.rs:878-914): the value seen by frame f is the one after f+1 ticks.  The same
-        // per-frame table carries the graph's stream inputs (`<stream_in>_block`, one row each, broadcast to every
-        // voice); a graph with stream inputs always runs the table-reading kernel variant.
-        const size_t stride = (size_t)OG_MAX_BLOCK * batch_cap;
-        const bool ramping = active_ramps > 0 && cg->n_ramps > 0;
-        if ((ramping || cg->n_streams > 0 || q_ramps) && cg->n_ramps + cg->n_streams > 0) {
-            if (q_ramp_slot < 0) { // first block of the queue that needs the table: earlier blocks get constant rows
-                q_ramp_slot = ramp_head;
-                ramp_head = (ramp_head + 1) % RAMP_RING;
-                batch_done(ramp_seq[q_ramp_slot]);
-                float* tab0 = h_ramp[q_ramp_slot];
-                for (size_t i = 0; i < cg->inputs.size(); ++i) {
-                    const int row = cg->inputs[i].ramp_row;
-                    if (row >= 0) std::fill(tab0 + (size_t)row * stride, tab0 + (size_t)row * stride + q_frames, ramps[i].current);
-                }
-            }
-            q_ramps = true;
-            float* tab = h_ramp[q_ramp_slot];
-            for (uint32_t f = 0; f < frames; ++f) {
-                for (size_t i = 0; i < cg->inputs.size(); ++i) {
-                    const int row = cg->inputs[i].ramp_row;
-                    if (row < 0) continue;
-                    if (active_ramps > 0 && ramps[i].tick()) active_ramps -= 1;
-                    tab[(size_t)row * stride + q_frames + f] = ramps[i].current;
-                }
-            }
-            for (size_t i = 0; i < cg->inputs.size(); ++i) {
-                if (cg->inputs[i].ramp_row >= 0) values[i] = ramps[i].current;
-                const int srow = cg->inputs[i].stream_row;
-                for (int k = 0; srow >= 0 && k < std::max(1, cg->inputs[i].decl.channels); ++k) // (planar: one row per channel)
-                    memcpy(tab + (size_t)(srow + k) * stride + q_frames, stream_blocks[i].data() + (size_t)k * OG_MAX_BLOCK, (size_t)frames * 4);
-            }
-        }
-        QueuedBlock qb;
-        qb.dst = d_out ? d_out : d_bus;
-        qb.frames = frames;
-        qb.trem_rate = qb.trem_depth = 0.0f;
-        qb.conv = 0;
-        if (conv_on()) { // voices.output -> reverb.input; reverb.output -> out
-            // Convolver::process (convolution/mod.rs:535-573): the outgoing response is dropped once pos reaches fade_len; a
-            // swap retires a response that is still fading out at once and fades from the current one, which keeps its history
-            if (conv.old && frame_now >= conv.fade_start + conv_fade_len()) conv_retire(conv.old);
-            if (conv_pending) {
-                conv_retire(conv.old);
-                conv.old = conv.cur;
-                conv.old_from = conv.cur_from;
-                conv.cur = conv_pending;
-                conv.cur_from = conv.fade_start = frame_now;
-                conv_pending.reset();
-            }
-            if (q_conv.empty() || !q_conv.back().same(conv)) q_conv.push_back(conv);
-            qb.conv = (uint32_t)q_conv.size() - 1;
-        }
-        if (cg->bus_stage == ogc::BusStage::Tremolo && bus_stage) { // voices.output -> tremolo.input; tremolo.output -> out (Frame<2>)
-            ogc::UEnv ev = env();
-            qb.trem_rate = cg->tremolo_rate(ev);
-            qb.trem_depth = cg->tremolo_depth(ev);
-        }
-        queue.push_back(qb);
-        q_frames += frames;
-        frame_now += frames;
-        last_frames = frames;
-        // The last ramp ended inside this block: launch what is queued, so that the blocks that follow -- nothing moves in
-        // them -- start a queue of their own on the kernel variant that does not read the table.  (Round 6, the moving-cutoff
-        // variant of the bench: the launch that held the 2 205-frame cutoff ramp also held the ~20 quiet blocks queued behind
-        // it and ran them 35 % slower -- per-frame parameter tests, table reads -- than the `_00` variant; a launch costs 25 us.)
-        const bool ramps_done = ramping && active_ramps == 0 && cg->n_streams == 0;
-        if (queue.size() >= bus_batch || n_taps > 0 || ramps_done) flush_bus();
-    }
-
-    // launch the queued blocks: voice kernel over their frames, bus reduce (fixed-association tree: groups of 1024
-    // rows, then, for > 1024 waves, the group sums), post-mix stage block by block
-    void flush_bus()
-    {
-        if (queue.empty()) return;
-        upload_events(); // (before the launch arguments are formed: a rebuild may move the timeline)
-        HostProf::Scope ps(prof, HostProf::LAUNCH);
-        OgBlockArgs A;
-        memset(&A, 0, sizeof A);
-        A.n_voices = V;
-        A.frames = q_frames;
-        A.ramp_stride = (uint32_t)((size_t)OG_MAX_BLOCK * batch_cap);
-        A.lanes = lanes;
-        A.split = split;
-        A.wide = wide ? 1u : 0u;
-        A.frame0 = q_frame0;
-        A.state = d_state;
-        A.lane_state = d_lane_state;
-        A.lane_dump = d_lane_state ? d_lane_state + cg->lane_state.size() * (size_t)V * cg->lpv * cg->lane_width : nullptr;
-        A.events = d_events;
-        A.ev_end = d_ev_end;
-        A.ev_cursor = d_ev_cursor;
-        A.partials = d_partials;
-        const uint32_t n_chunks16 = (q_frames + OG_RED_FRAMES - 1) / OG_RED_FRAMES;
-        A.partial_plane = (uint32_t)((size_t)n_chunks16 * n_wg * OG_RED_FRAMES);
-        A.taps = d_taps;
-        A.tap_slot = d_tap_slot;
-        A.out_ev = d_out_ev;
-        A.out_ev_cap = out_ev_cap;
-        A.out_ev_count = d_out_ev ? d_out_ev_count : nullptr;
-        A.ev_lost = d_out_ev_count ? d_out_ev_count + 1 : nullptr;
-        for (size_t k = 0; k < cg->rings.size(); ++k) {
-            A.rings[k] = d_ring[k];
-            A.ring_cap[k] = ring_cap[k];
-        }
-        // block-uniform slots: the values the queued blocks were queued under (a setter launches the queue before it
-        // changes one; ramped inputs are read from the table whenever a ramp moved inside the queue)
-        {
-            ogc::UEnv e = env();
-            uint32_t starts[OG_MAX_LAUNCH_BLOCKS + 1];
-            uint32_t acc = 0, nb = 0;
-            for (const QueuedBlock& qb : queue) {
-                if (nb < OG_MAX_LAUNCH_BLOCKS) starts[nb++] = acc;
-                acc += qb.frames;
-            }
-            e.block_starts = starts;
-            e.n_blocks = nb;
-            for (const auto& up : cg->uprogs) A.slots[up.dst] = up.fn(e);
-        }
-        if (cg->player_slot0 >= 0) { // SamplePlayer: the pool and the descriptor table (og_sample_player.hip.h)
-            uint32_t* ps = A.slots + cg->player_slot0;
-            ps[0] = (uint32_t)((uintptr_t)d_pool & 0xFFFFFFFFu);
-            ps[1] = (uint32_t)((uint64_t)(uintptr_t)d_pool >> 32);
-            ps[2] = (uint32_t)((uintptr_t)d_desc & 0xFFFFFFFFu);
-            ps[3] = (uint32_t)((uint64_t)(uintptr_t)d_desc >> 32);
-            ps[4] = sample_cap;
-        }
-        if (rcp_cover(release_need(A.slots))) {
-            A.rcp_tab = d_rcp;
-            A.rcp_len = rcp_n;
-        }
-        const bool ramps_on = q_ramps && q_ramp_slot >= 0;
-        if (ramps_on) {
-            const int r = q_ramp_slot;
-            const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
-            HIPCK(hipMemcpyAsync(d_ramp[r], h_ramp[r], rows * A.ramp_stride * 4, hipMemcpyHostToDevice, stream));
-            ramp_seq[r] = flush_seq + 1;
-            batch_staged = true;
-            A.ramp_table = d_ramp[r];
-        }
-        const bool taps_on = n_taps > 0;
-        const bool timed = timing && t_used < 8192; // (a host that never collects the timings stops adding events)
-        if (timed) {
-            if (t_used == t_start.size()) {
-                hipEvent_t a, b;
-                HIPCK(hipEventCreate(&a));
-                HIPCK(hipEventCreate(&b));
-                t_start.push_back(a);
-                t_stop.push_back(b);
-            }
-            HIPCK(hipEventRecord(t_start[t_used], stream));
-            if (!h_clock) {
-                HIPCK(hipHostMalloc((void**)&h_clock, T_CLOCK * 4 * sizeof(unsigned long long), hipHostMallocDefault));
-                memset(h_clock, 0, T_CLOCK * 4 * sizeof(unsigned long long));
-            }
-            A.clock_out = h_clock + 4 * t_used; // (pinned host memory is device-visible: four 8-byte stores per launch)
-        }
-        // The zero variant (og_graph.cpp, ZeroChain): every block of this launch was queued under these slot values (a setter
-        // launches the queue before it changes one) and no ramp ticks in it, so a zero slot here is +-0 on every frame.
-        bool zero = zero_spec && !ramps_on && !cg->zero_slots.empty();
-        for (int zs : cg->zero_slots) zero = zero && (A.slots[zs] & 0x7fffffffu) == 0u;
-        // The deeper zero variant (ZeroFolds) also needs finite operator levels -- in this launch and in every one before it:
-        // an inf or NaN an earlier launch left in an operator's prev_output stays there under the general kernel (NaN * 0).
-        for (int fs : cg->finite_slots) guards_held = guards_held && (A.slots[fs] & 0x7f800000u) != 0x7f800000u;
-        bool zero2 = zero_spec && zero2_spec && guards_held && !ramps_on && !cg->zero2_slots.empty();
-        for (int zs : cg->zero2_slots) zero2 = zero2 && (A.slots[zs] & 0x7fffffffu) == 0u;
-        last_zero = false;
-        last_tier = 0;
-        // (OSCEN_GPU_STAGE_SPEC=0: the deeper variant without its stage-uniform envelope bodies -- the switch is the last uniform
-        //  slot, which a graph that has the bodies does not use, og_stage_uniform.hip.h; the other kernels never read it)
-        if (zero2 && !stage_spec && cg->stage_spec) A.slots[OG_MAX_SLOTS - 1] = 1u;
-        if (zero2 && (launch ? launch_zero2 != nullptr : jit->launch_zero2(A, taps_on, stream))) {
-            if (launch) launch_zero2(A, taps_on, stream);
-            last_zero = true;
-            last_tier = 2;
-        } else if (launch && zero && launch_zero) {
-            launch_zero(A, taps_on, stream);
-            last_zero = true;
-        } else if (launch) {
-            launch(A, ramps_on, taps_on, stream);
-        } else if (zero) {
-            last_zero = jit->launch_zero(A, taps_on, stream);
-        } else {
-            jit->launch(A, ramps_on, taps_on, stream);
-        }
-        if (last_zero && last_tier == 0) last_tier = 1;
-        if (timed) {
-            HIPCK(hipEventRecord(t_stop[t_used], stream));
-            ++t_used;
-            t_blocks += queue.size();
-        }
-        HIPCK(hipGetLastError());
-        // ---- bus: sum the partial rows ----------------------------------------------------------------
-        const bool post_mix = cg->bus_stage == ogc::BusStage::Tremolo && bus_stage;
-        const bool post_conv = conv_on();
-        const uint32_t ch = cg->voice_channels; // summed voices: mono, or Frame<2> voices (a post-mix node writes its Frame<2> bus itself)
-        bool contiguous = !post_mix;
-        for (size_t k = 1; k < queue.size() && contiguous; ++k)
-            contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * ch;
-        float* sum_dst = post_mix ? d_mono : (contiguous ? queue[0].dst : d_stage_bus);
-        float* const wet_dst = sum_dst;
-        if (post_conv) { // the dry sum goes behind the history; when the buffer is full the newest hist_keep frames move to its front
-            if (hist_pos + q_frames > hist_len) {
-                const uint32_t n = (uint32_t)(hist_keep * ch);
-                hipLaunchKernelGGL(og_bus_conv_move, dim3((n + 255) / 256), dim3(256), 0, stream, d_hist + (hist_pos - hist_keep) * ch, d_hist, n);
-                hist_pos = hist_keep;
-            }
-            sum_dst = d_hist + hist_pos * ch;
-        }
-        for (uint32_t c = 0; c < ch; ++c) { // one tree per channel plane; the last pass interleaves Frame<2> samples
-            const float* src = d_partials + (size_t)c * A.partial_plane;
-            uint32_t rows = n_wg;
-            float* tmp = d_partials2;
-            bus_passes = 1;
-            while (rows > OG_RED_GROUP) {
-                bus_passes += 1;
-                const uint32_t groups = (rows + OG_RED_GROUP - 1) / OG_RED_GROUP;
-                hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, groups), dim3(1024), 0, stream, src, rows, q_frames, tmp, 1u, 0u);
-                src = tmp;
-                rows = groups;
-                tmp = tmp + (size_t)groups * n_chunks16 * OG_RED_FRAMES; // next level writes behind this one
-            }
-            hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
-        }
-        HIPCK(hipGetLastError());
-        if (post_conv) { // one pass per run of blocks queued under the same responses -- as a rule the whole batch
-            const uint32_t fade_len = conv_fade_len();
-            for (size_t b0 = 0, f0 = 0; b0 < queue.size();) {
-                size_t b1 = b0;
-                uint32_t nf = 0;
-                while (b1 < queue.size() && queue[b1].conv == queue[b0].conv) nf += queue[b1++].frames;
-                const ConvCfg& cf = q_conv[queue[b0].conv];
-                const uint64_t t0 = q_frame0 + f0;
-                const int64_t buf_lo = -(int64_t)(hist_pos + f0);
-                auto response = [&](const std::shared_ptr<ConvIR>& ir, uint64_t from, uint32_t frames, float* rows) {
-                    OgConvResponse r;
-                    r.taps = ir ? ir->d : nullptr;
-                    r.n_taps = ir ? ir->K() : 0u;
-                    r.n_frames = frames;
-                    r.lo = (int32_t)std::max<int64_t>(buf_lo, from >= t0 ? (int64_t)std::min<uint64_t>(from - t0, 0x7fffffffu) : -(int64_t)std::min<uint64_t>(t0 - from, 0x7fffffffu));
-                    r.rows = rows;
-                    return r;
-                };
-                const uint64_t fade_end = cf.fade_start + fade_len;
-                const OgConvResponse rc = response(cf.cur, cf.cur_from, nf, d_conv_rows);
-                const OgConvResponse ro = response(cf.old, cf.old_from, (cf.old && t0 < fade_end) ? (uint32_t)std::min<uint64_t>(nf, fade_end - t0) : 0u,
-                                                   d_conv_rows + conv_rows_half);
-                const float* x = d_hist + (hist_pos + f0) * ch;
-                for (const OgConvResponse* r : {&rc, &ro})
-                    if (r->n_frames && r->n_taps)
-                        hipLaunchKernelGGL(og_bus_conv, dim3((r->n_frames + OG_CONV_F - 1) / OG_CONV_F, (r->n_taps + OG_CONV_S - 1) / OG_CONV_S, ch),
-                                           dim3(OG_CONV_LANES), 0, stream, x, ch, *r, conv_row_stride);
-                hipLaunchKernelGGL(og_bus_conv_finish, dim3((nf + 255) / 256, ch), dim3(256), 0, stream, rc, ro, ch, conv_row_stride,
-                                   (uint32_t)(t0 - cf.fade_start), fade_len, wet_dst + f0 * ch);
-                b0 = b1;
-                f0 += nf;
-            }
-            hist_pos += q_frames;
-            q_conv.clear();
-            HIPCK(hipGetLastError());
-        }
-        size_t off = 0;
-        for (const QueuedBlock& qb : queue) {
-            if (post_mix) {
-                hipLaunchKernelGGL(og_bus_tremolo, dim3(1), dim3(512), 0, stream, d_mono + off, qb.frames, qb.trem_rate, qb.trem_depth, sr,
-                                   d_bus_phase, qb.dst);
-            } else if (!contiguous) {
-                HIPCK(hipMemcpyAsync(qb.dst, d_stage_bus + off * ch, (size_t)qb.frames * ch * 4, hipMemcpyDeviceToDevice, stream));
-            }
-            off += qb.frames;
-        }
-        HIPCK(hipGetLastError());
-        flush_seq += 1;
-        if (batch_staged) { // this batch read a host staging buffer: tell the host when the stream is past it
-            if (!h_progress) {
-                HIPCK(hipHostMalloc((void**)&h_progress, 64, hipHostMallocCoherent)); // (fine-grained: a device store is visible to the host while the stream runs)
-                *h_progress = 0;
-            }
-            hipLaunchKernelGGL(og_stream_mark, dim3(1), dim3(1), 0, stream, h_progress, flush_seq);
-            HIPCK(hipGetLastError());
-            batch_staged = false;
-        }
-        queue.clear();
+void og_engine::process_async(uint32_t frames, float* d_out)
+{
+    HIPCK(hipSetDevice(device));
+    tl.drop_late_local(frame_now + frames);
+    // events wait on the host until the queue is launched: launch it before they outgrow the staging buffers (or the
+    // size up to which per-voice segments beat a rebuild of the whole timeline)
+    if (!queue.empty() && tl.n_pending() > std::min<size_t>(tl.stage_events() / 2, (size_t)V / 4 + 32)) flush_bus();
+    if (queue.empty()) {
+        q_frame0 = frame_now;
         q_frames = 0;
+        q_ramps = cg->n_streams > 0;
+        q_ramp_slot = -1;
     }
-};
+    // tick_ramps (codegen/mod.rs:878-914): the value seen by frame f is the one after f+1 ticks.  The same
+    // per-frame table carries the graph's stream inputs (`<stream_in>_block`, one row each, broadcast to every
+    // voice); a graph with stream inputs always runs the table-reading kernel variant.
+    const size_t stride = (size_t)OG_MAX_BLOCK * batch_cap;
+    const bool ramping = active_ramps > 0 && cg->n_ramps > 0;
+    if ((ramping || cg->n_streams > 0 || q_ramps) && cg->n_ramps + cg->n_streams > 0) {
+        if (q_ramp_slot < 0) { // first block of the queue that needs the table: earlier blocks get constant rows
+            q_ramp_slot = ramp_head;
+            ramp_head = (ramp_head + 1) % RAMP_RING;
+            batch_done(ramp_seq[q_ramp_slot]);
+            float* tab0 = h_ramp[q_ramp_slot];
+            for (size_t i = 0; i < cg->inputs.size(); ++i) {
+                const int row = cg->inputs[i].ramp_row;
+                if (row >= 0) std::fill(tab0 + (size_t)row * stride, tab0 + (size_t)row * stride + q_frames, ramps[i].current);
+            }
+        }
+        q_ramps = true;
+        float* tab = h_ramp[q_ramp_slot];
+        for (uint32_t f = 0; f < frames; ++f) {
+            for (size_t i = 0; i < cg->inputs.size(); ++i) {
+                const int row = cg->inputs[i].ramp_row;
+                if (row < 0) continue;
+                if (active_ramps > 0 && ramps[i].tick()) active_ramps -= 1;
+                tab[(size_t)row * stride + q_frames + f] = ramps[i].current;
+            }
+        }
+        for (size_t i = 0; i < cg->inputs.size(); ++i) {
+            if (cg->inputs[i].ramp_row >= 0) values[i] = ramps[i].current;
+            const int srow = cg->inputs[i].stream_row;
+            for (int k = 0; srow >= 0 && k < std::max(1, cg->inputs[i].decl.channels); ++k) // (planar: one row per channel)
+                memcpy(tab + (size_t)(srow + k) * stride + q_frames, stream_blocks[i].data() + (size_t)k * OG_MAX_BLOCK, (size_t)frames * 4);
+        }
+    }
+    QueuedBlock qb;
+    qb.dst = d_out ? d_out : d_bus;
+    qb.frames = frames;
+    qb.trem_rate = qb.trem_depth = 0.0f;
+    qb.conv = 0;
+    if (conv_on()) { // voices.output -> reverb.input; reverb.output -> out
+        // Convolver::process (convolution/mod.rs:535-573): the outgoing response is dropped once pos reaches fade_len; a
+        // swap retires a response that is still fading out at once and fades from the current one, which keeps its history
+        if (conv.old && frame_now >= conv.fade_start + conv_fade_len()) conv_retire(conv.old);
+        if (conv_pending) {
+            conv_retire(conv.old);
+            conv.old = conv.cur;
+            conv.old_from = conv.cur_from;
+            conv.cur = conv_pending;
+            conv.cur_from = conv.fade_start = frame_now;
+            conv_pending.reset();
+        }
+        if (q_conv.empty() || !q_conv.back().same(conv)) q_conv.push_back(conv);
+        qb.conv = (uint32_t)q_conv.size() - 1;
+    }
+    if (cg->bus_stage == ogc::BusStage::Tremolo && bus_stage) { // voices.output -> tremolo.input; tremolo.output -> out (Frame<2>)
+        ogc::UEnv ev = env();
+        qb.trem_rate = cg->tremolo_rate(ev);
+        qb.trem_depth = cg->tremolo_depth(ev);
+    }
+    queue.push_back(qb);
+    q_frames += frames;
+    frame_now += frames;
+    last_frames = frames;
+    // The last ramp ended inside this block: launch what is queued, so that the blocks that follow -- nothing moves in
+    // them -- start a queue of their own on the kernel variant that does not read the table.  (Round 6, the moving-cutoff
+    // variant of the bench: the launch that held the 2 205-frame cutoff ramp also held the ~20 quiet blocks queued behind
+    // it and ran them 35 % slower -- per-frame parameter tests, table reads -- than the `_00` variant; a launch costs 25 us.)
+    const bool ramps_done = ramping && active_ramps == 0 && cg->n_streams == 0;
+    if (queue.size() >= bus_batch || n_taps > 0 || ramps_done) flush_bus();
+}
+
+void og_engine::flush_bus()
+{
+    if (queue.empty()) return;
+    upload_events(); // (before the launch arguments are formed: a rebuild may move the timeline)
+    HostProf::Scope ps(prof, HostProf::LAUNCH);
+    OgBlockArgs A;
+    memset(&A, 0, sizeof A);
+    A.n_voices = V;
+    A.frames = q_frames;
+    A.ramp_stride = (uint32_t)((size_t)OG_MAX_BLOCK * batch_cap);
+    A.lanes = lanes;
+    A.split = split;
+    A.wide = wide ? 1u : 0u;
+    A.frame0 = q_frame0;
+    A.state = d_state;
+    A.lane_state = d_lane_state;
+    A.lane_dump = d_lane_state ? d_lane_state + cg->lane_state.size() * (size_t)V * cg->lpv * cg->lane_width : nullptr;
+    A.events = d_events;
+    A.ev_end = d_ev_end;
+    A.ev_cursor = d_ev_cursor;
+    A.partials = d_partials;
+    const uint32_t n_chunks16 = (q_frames + OG_RED_FRAMES - 1) / OG_RED_FRAMES;
+    A.partial_plane = (uint32_t)((size_t)n_chunks16 * n_wg * OG_RED_FRAMES);
+    A.taps = d_taps;
+    A.tap_slot = d_tap_slot;
+    A.out_ev = d_out_ev;
+    A.out_ev_cap = out_ev_cap;
+    A.out_ev_count = d_out_ev ? d_out_ev_count : nullptr;
+    A.ev_lost = d_out_ev_count ? d_out_ev_count + 1 : nullptr;
+    for (size_t k = 0; k < cg->rings.size(); ++k) {
+        A.rings[k] = d_ring[k];
+        A.ring_cap[k] = ring_cap[k];
+    }
+    // block-uniform slots: the values the queued blocks were queued under (a setter launches the queue before it
+    // changes one; ramped inputs are read from the table whenever a ramp moved inside the queue)
+    {
+        ogc::UEnv e = env();
+        uint32_t starts[OG_MAX_LAUNCH_BLOCKS + 1];
+        uint32_t acc = 0, nb = 0;
+        for (const QueuedBlock& qb : queue) {
+            if (nb < OG_MAX_LAUNCH_BLOCKS) starts[nb++] = acc;
+            acc += qb.frames;
+        }
+        e.block_starts = starts;
+        e.n_blocks = nb;
+        for (const auto& up : cg->uprogs) A.slots[up.dst] = up.fn(e);
+    }
+    if (cg->player_slot0 >= 0) { // SamplePlayer: the pool and the descriptor table (og_sample_player.hip.h)
+        uint32_t* ps = A.slots + cg->player_slot0;
+        ps[0] = (uint32_t)((uintptr_t)d_pool & 0xFFFFFFFFu);
+        ps[1] = (uint32_t)((uint64_t)(uintptr_t)d_pool >> 32);
+        ps[2] = (uint32_t)((uintptr_t)d_desc & 0xFFFFFFFFu);
+        ps[3] = (uint32_t)((uint64_t)(uintptr_t)d_desc >> 32);
+        ps[4] = sample_cap;
+    }
+    if (rcp_cover(release_need(A.slots))) {
+        A.rcp_tab = d_rcp;
+        A.rcp_len = rcp_n;
+    }
+    const bool ramps_on = q_ramps && q_ramp_slot >= 0;
+    if (ramps_on) {
+        const int r = q_ramp_slot;
+        const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
+        HIPCK(hipMemcpyAsync(d_ramp[r], h_ramp[r], rows * A.ramp_stride * 4, hipMemcpyHostToDevice, stream));
+        ramp_seq[r] = flush_seq + 1;
+        batch_staged = true;
+        A.ramp_table = d_ramp[r];
+    }
+    const bool taps_on = n_taps > 0;
+    const bool timed = timing && t_used < 8192; // (a host that never collects the timings stops adding events)
+    if (timed) {
+        if (t_used == t_start.size()) {
+            hipEvent_t a, b;
+            HIPCK(hipEventCreate(&a));
+            HIPCK(hipEventCreate(&b));
+            t_start.push_back(a);
+            t_stop.push_back(b);
+        }
+        HIPCK(hipEventRecord(t_start[t_used], stream));
+        if (!h_clock) {
+            HIPCK(hipHostMalloc((void**)&h_clock, T_CLOCK * 4 * sizeof(unsigned long long), hipHostMallocDefault));
+            memset(h_clock, 0, T_CLOCK * 4 * sizeof(unsigned long long));
+        }
+        A.clock_out = h_clock + 4 * t_used; // (pinned host memory is device-visible: four 8-byte stores per launch)
+    }
+    // The zero variant (og_graph.cpp, ZeroChain): every block of this launch was queued under these slot values (a setter
+    // launches the queue before it changes one) and no ramp ticks in it, so a zero slot here is +-0 on every frame.
+    bool zero = zero_spec && !ramps_on && !cg->zero_slots.empty();
+    for (int zs : cg->zero_slots) zero = zero && (A.slots[zs] & 0x7fffffffu) == 0u;
+    // The deeper zero variant (ZeroFolds) also needs finite operator levels -- in this launch and in every one before it:
+    // an inf or NaN an earlier launch left in an operator's prev_output stays there under the general kernel (NaN * 0).
+    for (int fs : cg->finite_slots) guards_held = guards_held && (A.slots[fs] & 0x7f800000u) != 0x7f800000u;
+    bool zero2 = zero_spec && zero2_spec && guards_held && !ramps_on && !cg->zero2_slots.empty();
+    for (int zs : cg->zero2_slots) zero2 = zero2 && (A.slots[zs] & 0x7fffffffu) == 0u;
+    last_zero = false;
+    last_tier = 0;
+    // (OSCEN_GPU_STAGE_SPEC=0: the deeper variant without its stage-uniform envelope bodies -- the switch is the last uniform
+    //  slot, which a graph that has the bodies does not use, og_stage_uniform.hip.h; the other kernels never read it)
+    if (zero2 && !stage_spec && cg->stage_spec) A.slots[OG_MAX_SLOTS - 1] = 1u;
+    if (zero2 && (launch ? launch_zero2 != nullptr : jit->launch_zero2(A, taps_on, stream))) {
+        if (launch) launch_zero2(A, taps_on, stream);
+        last_zero = true;
+        last_tier = 2;
+    } else if (launch && zero && launch_zero) {
+        launch_zero(A, taps_on, stream);
+        last_zero = true;
+    } else if (launch) {
+        launch(A, ramps_on, taps_on, stream);
+    } else if (zero) {
+        last_zero = jit->launch_zero(A, taps_on, stream);
+    } else {
+        jit->launch(A, ramps_on, taps_on, stream);
+    }
+    if (last_zero && last_tier == 0) last_tier = 1;
+    if (timed) {
+        HIPCK(hipEventRecord(t_stop[t_used], stream));
+        ++t_used;
+        t_blocks += queue.size();
+    }
+    HIPCK(hipGetLastError());
+    // ---- bus: sum the partial rows ----------------------------------------------------------------
+    const bool post_mix = cg->bus_stage == ogc::BusStage::Tremolo && bus_stage;
+    const bool post_conv = conv_on();
+    const uint32_t ch = cg->voice_channels; // summed voices: mono, or Frame<2> voices (a post-mix node writes its Frame<2> bus itself)
+    bool contiguous = !post_mix;
+    for (size_t k = 1; k < queue.size() && contiguous; ++k)
+        contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * ch;
+    float* sum_dst = post_mix ? d_mono : (contiguous ? queue[0].dst : d_stage_bus);
+    float* const wet_dst = sum_dst;
+    if (post_conv) { // the dry sum goes behind the history; when the buffer is full the newest hist_keep frames move to its front
+        if (hist_pos + q_frames > hist_len) {
+            const uint32_t n = (uint32_t)(hist_keep * ch);
+            hipLaunchKernelGGL(og_bus_conv_move, dim3((n + 255) / 256), dim3(256), 0, stream, d_hist + (hist_pos - hist_keep) * ch, d_hist, n);
+            hist_pos = hist_keep;
+        }
+        sum_dst = d_hist + hist_pos * ch;
+    }
+    for (uint32_t c = 0; c < ch; ++c) { // one tree per channel plane; the last pass interleaves Frame<2> samples
+        const float* src = d_partials + (size_t)c * A.partial_plane;
+        uint32_t rows = n_wg;
+        float* tmp = d_partials2;
+        bus_passes = 1;
+        while (rows > OG_RED_GROUP) {
+            bus_passes += 1;
+            const uint32_t groups = (rows + OG_RED_GROUP - 1) / OG_RED_GROUP;
+            hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, groups), dim3(1024), 0, stream, src, rows, q_frames, tmp, 1u, 0u);
+            src = tmp;
+            rows = groups;
+            tmp = tmp + (size_t)groups * n_chunks16 * OG_RED_FRAMES; // next level writes behind this one
+        }
+        hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
+    }
+    HIPCK(hipGetLastError());
+    if (post_conv) { // one pass per run of blocks queued under the same responses -- as a rule the whole batch
+        const uint32_t fade_len = conv_fade_len();
+        for (size_t b0 = 0, f0 = 0; b0 < queue.size();) {
+            size_t b1 = b0;
+            uint32_t nf = 0;
+            while (b1 < queue.size() && queue[b1].conv == queue[b0].conv) nf += queue[b1++].frames;
+            const ConvCfg& cf = q_conv[queue[b0].conv];
+            const uint64_t t0 = q_frame0 + f0;
+            const int64_t buf_lo = -(int64_t)(hist_pos + f0);
+            auto response = [&](const std::shared_ptr<ConvIR>& ir, uint64_t from, uint32_t frames, float* rows) {
+                OgConvResponse r;
+                r.taps = ir ? ir->d : nullptr;
+                r.n_taps = ir ? ir->K() : 0u;
+                r.n_frames = frames;
+                r.lo = (int32_t)std::max<int64_t>(buf_lo, from >= t0 ? (int64_t)std::min<uint64_t>(from - t0, 0x7fffffffu) : -(int64_t)std::min<uint64_t>(t0 - from, 0x7fffffffu));
+                r.rows = rows;
+                return r;
+            };
+            const uint64_t fade_end = cf.fade_start + fade_len;
+            const OgConvResponse rc = response(cf.cur, cf.cur_from, nf, d_conv_rows);
+            const OgConvResponse ro = response(cf.old, cf.old_from, (cf.old && t0 < fade_end) ? (uint32_t)std::min<uint64_t>(nf, fade_end - t0) : 0u,
+                                               d_conv_rows + conv_rows_half);
+            const float* x = d_hist + (hist_pos + f0) * ch;
+            for (const OgConvResponse* r : {&rc, &ro})
+                if (r->n_frames && r->n_taps)
+                    hipLaunchKernelGGL(og_bus_conv, dim3((r->n_frames + OG_CONV_F - 1) / OG_CONV_F, (r->n_taps + OG_CONV_S - 1) / OG_CONV_S, ch),
+                                       dim3(OG_CONV_LANES), 0, stream, x, ch, *r, conv_row_stride);
+            hipLaunchKernelGGL(og_bus_conv_finish, dim3((nf + 255) / 256, ch), dim3(256), 0, stream, rc, ro, ch, conv_row_stride,
+                               (uint32_t)(t0 - cf.fade_start), fade_len, wet_dst + f0 * ch);
+            b0 = b1;
+            f0 += nf;
+        }
+        hist_pos += q_frames;
+        q_conv.clear();
+        HIPCK(hipGetLastError());
+    }
+    size_t off = 0;
+    for (const QueuedBlock& qb : queue) {
+        if (post_mix) {
+            hipLaunchKernelGGL(og_bus_tremolo, dim3(1), dim3(512), 0, stream, d_mono + off, qb.frames, qb.trem_rate, qb.trem_depth, sr,
+                               d_bus_phase, qb.dst);
+        } else if (!contiguous) {
+            HIPCK(hipMemcpyAsync(qb.dst, d_stage_bus + off * ch, (size_t)qb.frames * ch * 4, hipMemcpyDeviceToDevice, stream));
+        }
+        off += qb.frames;
+    }
+    HIPCK(hipGetLastError());
+    flush_seq += 1;
+    if (batch_staged) { // this batch read a host staging buffer: tell the host when the stream is past it
+        if (!h_progress) {
+            HIPCK(hipHostMalloc((void**)&h_progress, 64, hipHostMallocCoherent)); // (fine-grained: a device store is visible to the host while the stream runs)
+            *h_progress = 0;
+        }
+        hipLaunchKernelGGL(og_stream_mark, dim3(1), dim3(1), 0, stream, h_progress, flush_seq);
+        HIPCK(hipGetLastError());
+        batch_staged = false;
+    }
+    queue.clear();
+    q_frames = 0;
+}
+
+void og_engine::launch_bus_tremolo(const float* mono, uint32_t frames, float rate, float depth, float sr, float* phase_state, float* out,
+                                   hipStream_t stream)
+{
+    hipLaunchKernelGGL(og_bus_tremolo, dim3(1), dim3(512), 0, stream, mono, frames, rate, depth, sr, phase_state, out);
+}
 
 namespace {
-
-using ogabi::guard; // Error (carries its OG_E_* code) / bad_alloc / std::exception -> code + og_last_error(); og_abi.h
 
 int check_value_input(const og_engine* e, uint32_t input, bool per_voice)
 {
@@ -1926,21 +858,11 @@ int push_event(og_engine* e, uint32_t input, uint32_t voice, uint64_t frame, flo
         target = (uint32_t)in.event_index;
     }
     if (local && !setvalue) { // ArrayVec<EventInstance, 32> capacity per endpoint per block
-        const size_t ne = (size_t)std::max(1, e->cg->n_event_inputs);
-        if (e->local_cnt.empty()) e->local_cnt.assign((size_t)e->V * ne, 0);
-        const size_t k = (size_t)voice * ne + target;
-        uint8_t& cnt = e->local_cnt[k];
-        if (cnt < OG_MAX_EVENTS_PER_BLOCK) {
-            if (cnt == 0) e->local_touched.push_back((uint32_t)k);
-            cnt += 1;
-        } else {
-            e->dropped += 1;
+        if (!e->tl.count_local(voice, target, (size_t)std::max(1, e->cg->n_event_inputs), OG_MAX_EVENTS_PER_BLOCK))
             return set_err(OG_E_OVERFLOW, "event queue full (32 per voice per input per block): event dropped");
-        }
     }
     // (an event scheduled in the past fires on the first frame of the next block, like a late event on the device)
-    e->pending.push_back(HostEvent{voice, std::max(frame, e->frame_now), target, value, e->seq++, local});
-    if (local) e->n_block_local += 1;
+    e->tl.push(voice, std::max(frame, e->frame_now), target, value, local);
     return OG_OK;
 }
 
@@ -2347,7 +1269,9 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             if (const char* zs = ogabi::experiment_knob("OSCEN_GPU_ZERO2_SPEC")) e->zero2_spec = atoi(zs) != 0;
             if (const char* ss = ogabi::experiment_knob("OSCEN_GPU_STAGE_SPEC")) e->stage_spec = atoi(ss) != 0;
             if (const char* rc = ogabi::experiment_knob("OSCEN_GPU_RCP_CAP")) e->rcp_cap = std::min<uint32_t>(OG_RCP_MAX, (uint32_t)atoll(rc));
-            if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) e->ev_headroom_env = std::max<size_t>(64, (size_t)atoll(hv));
+            size_t headroom = EventTimeline::HEADROOM;
+            if (const char* hv = ogabi::experiment_knob("OSCEN_GPU_EV_HEADROOM")) headroom = std::max<size_t>(64, (size_t)atoll(hv));
+            e->tl = EventTimeline(n_voices, EventTimeline::STAGE_EVENTS, headroom);
             uint32_t lanes = OG_WAVE;
             if (const char* ev = ogabi::experiment_knob("OSCEN_GPU_LANES")) {
                 const int l = atoi(ev);
@@ -2864,9 +1788,9 @@ int og_schedule_voice_events(og_engine* e, uint32_t input, uint32_t n, const uin
     else return set_err(OG_E_INVALID, "'" + in.decl.name + "' is neither an event input nor a per-voice value input");
     for (uint32_t i = 0; i < n; ++i)
         if (voices[i] >= e->V) return set_err(OG_E_INVALID, "voice index out of range");
-    e->pending.reserve(e->pending.size() + n);
+    e->tl.reserve_pending(n);
     for (uint32_t i = 0; i < n; ++i)
-        e->pending.push_back(HostEvent{e->phys(voices[i]), std::max(abs_frames[i], e->frame_now), target, values[i], e->seq++, false});
+        e->tl.push(e->phys(voices[i]), std::max(abs_frames[i], e->frame_now), target, values[i], false);
     return OG_OK;
     });
 }
@@ -2880,7 +1804,7 @@ int og_process_block_async(og_engine* e, uint32_t frames, float* d_out_bus)
         if (frames == 0) { // process_block(0): no frame runs; events queued for the block are discarded with it
             HIPCK(hipSetDevice(e->device));
             e->flush_bus();
-            e->drop_late_local(0);
+            e->tl.drop_late_local(e->frame_now);
             e->last_frames = 0;
             return OG_OK;
         }
@@ -3231,7 +2155,7 @@ int og_uses_split_kernel(const og_engine* e) { return e ? (int)e->split : 0; }
 uint32_t og_voices_per_wave(const og_engine* e) { return e ? e->lanes / (uint32_t)e->cg->lpv : 0; }
 // Side-effect free (a monitoring thread may poll it while the audio thread renders): host-side drops plus what
 // og_sync_event_counters() last folded in from the device.
-uint64_t og_events_dropped(const og_engine* e) { return e ? e->dropped + e->ev_lost_total : 0; }
+uint64_t og_events_dropped(const og_engine* e) { return e ? e->tl.dropped + e->ev_lost_total : 0; }
 
 // in-voice event queues (#[output(event)] fields of user nodes) hold OG_NODE_EVENTS_PER_FRAME events per frame and
 // output; what they could not hold is counted on the device.  This launches the queued blocks, reads that counter back
@@ -3337,21 +2261,20 @@ int og_kernel_fold_tier(const og_engine* e) { return e ? e->last_tier : 0; }
 int og_event_stats(const og_engine* e, uint64_t* full_rebuilds, uint64_t* incremental_updates, uint64_t* resident_events)
 {
     if (!e) return set_err(OG_E_INVALID, "null engine");
-    if (full_rebuilds) *full_rebuilds = e->n_full_rebuilds;
-    if (incremental_updates) *incremental_updates = e->n_incremental;
-    if (resident_events) *resident_events = (uint64_t)e->ev_tail;
+    if (full_rebuilds) *full_rebuilds = e->tl.n_full_rebuilds;
+    if (incremental_updates) *incremental_updates = e->tl.n_incremental;
+    if (resident_events) *resident_events = (uint64_t)e->tl.resident_events();
     return OG_OK;
 }
 
-uint64_t og_event_ring_wraps(const og_engine* e) { return e ? e->n_ring_wraps : 0; }
-uint64_t og_events_copied(const og_engine* e) { return e ? e->n_events_copied : 0; }
+uint64_t og_event_ring_wraps(const og_engine* e) { return e ? e->tl.n_ring_wraps : 0; }
+uint64_t og_events_copied(const og_engine* e) { return e ? e->tl.n_events_copied : 0; }
 
 int og_reserve_events(og_engine* e, uint64_t n_events)
 {
     if (!e) return set_err(OG_E_INVALID, "null engine");
     if (n_events > 0xF0000000ull) return set_err(OG_E_INVALID, "og_reserve_events: at most 2^32 - 2^28 events");
-    e->ev_reserve = (size_t)n_events;
-    e->ev_rebuild = e->ev_rebuild || (e->d_events && e->ev_tail + e->ev_reserve > e->ev_cap); // takes effect with the next rebuild
+    e->tl.reserve((size_t)n_events, e->d_events != nullptr); // takes effect with the next rebuild
     return OG_OK;
 }
 
@@ -3369,7 +2292,7 @@ int og_group_voices(og_engine* e, uint32_t policy)
     if (!e) return set_err(OG_E_INVALID, "null engine");
     if (policy > 2u) return set_err(OG_E_INVALID, "og_group_voices: policy 0 (identity), 1 (by first note-off) or 2 (1 + waves dealt out by weight)");
     if (!e->inited) return set_err(OG_E_STATE, "og_init must be called before og_group_voices");
-    if (e->frame_now != 0 || !e->queue.empty() || !e->h_events.empty() || e->n_block_local != 0)
+    if (e->frame_now != 0 || !e->queue.empty() || e->tl.has_resident() || e->tl.n_local() != 0)
         return set_err(OG_E_STATE, "og_group_voices: only before the first block (and before block-local pushes)");
     if (e->n_taps != 0) return set_err(OG_E_STATE, "og_group_voices: set the voice taps after grouping");
     return guard([&] {
@@ -3381,7 +2304,7 @@ int og_group_voices(og_engine* e, uint32_t policy)
         } else {
             const uint64_t NONE = ~(uint64_t)0;
             std::vector<uint64_t> first_off(V, NONE), first_any(V, NONE);
-            for (const HostEvent& h : e->pending) {
+            for (const HostEvent& h : e->tl.pending_events()) {
                 const uint32_t v = e->logical(h.voice);
                 first_any[v] = std::min(first_any[v], h.frame);
                 if (!(h.target & OG_EV_SETVALUE) && h.value <= 0.0f) first_off[v] = std::min(first_off[v], h.frame);
@@ -3403,7 +2326,7 @@ int og_group_voices(og_engine* e, uint32_t policy)
                 std::vector<uint32_t> weight(W, 0u), rank(W);
                 std::vector<uint32_t> slot_of(V);
                 for (uint32_t r = 0; r < V; ++r) slot_of[order[r]] = r;
-                for (const HostEvent& h : e->pending) weight[slot_of[e->logical(h.voice)] / OG_WAVE] += 1u;
+                for (const HostEvent& h : e->tl.pending_events()) weight[slot_of[e->logical(h.voice)] / OG_WAVE] += 1u;
                 for (uint32_t w = 0; w < W; ++w) rank[w] = w;
                 std::stable_sort(rank.begin(), rank.end(), [&](uint32_t a, uint32_t b) { return weight[a] > weight[b]; });
                 std::vector<uint32_t> place(W); // place[k] = position of the k-th heaviest group
@@ -3443,7 +2366,7 @@ int og_group_voices(og_engine* e, uint32_t policy)
             e->bounce.h2d(d, moved.data(), (size_t)V * 4, e->stream);
             HIPCK(hipStreamSynchronize(e->stream));
         }
-        for (HostEvent& h : e->pending) h.voice = new_phys[e->logical(h.voice)];
+        e->tl.remap_pending([&](uint32_t slot) { return new_phys[e->logical(slot)]; });
         bool identity = true;
         for (uint32_t v = 0; v < V && identity; ++v) identity = new_phys[v] == v;
         if (identity) {
@@ -3535,412 +2458,3 @@ int og_shader_clock_ghz(og_engine* e, double* ghz)
 }
 
 } // extern "C"
-
-// ---- state snapshot ---------------------------------------------------------------------------------------------
-// blob = DSP state (state planes, lane arrays, post-mix phase, delay lines) + control block: frame counter, the value
-// and ValueRampState of every input, the ramp counter and every event that has not fired yet (resident timeline and
-// queued pushes).  Loading it into an engine of the same graph / voice count / sample rate continues the render
-// sample for sample.
-namespace {
-struct SnapHeader {
-    uint32_t magic, version;
-    uint64_t frame_now;
-    uint32_t n_inputs, active_ramps;
-    uint64_t n_events;
-};
-struct SnapRamp {
-    float current, target, increment;
-    uint32_t frames_remaining;
-};
-struct SnapEvent {
-    uint32_t voice, target;
-    uint64_t frame;
-    float value;
-    uint32_t block_local;
-};
-constexpr uint32_t SNAP_MAGIC = 0x3253474Fu; // "OGS2"
-// Post-mix Convolver: a section of its own BEHIND everything else (its size depends on the live responses, which a blob
-// brings along): header, taps of the current response, taps of the outgoing one, then the history -- the last
-// max(K) - 1 frames of the dry bus, interleaved.  A swap that no block has picked up yet is not part of the state.
-struct SnapConv {
-    uint32_t magic, channels;
-    uint32_t k_cur, k_old; // k_old = 0xFFFFFFFF: no fade in progress
-    uint64_t cur_from, old_from, fade_start;
-    uint32_t hist_frames, reserved;
-};
-constexpr uint32_t SNAP_CONV_MAGIC = 0x56434E4Fu; // "ONCV"
-size_t conv_hist_frames(const og_engine* e)
-{
-    const uint32_t k = std::max(e->conv.cur ? e->conv.cur->K() : 0u, e->conv.old ? e->conv.old->K() : 0u);
-    return k ? k - 1 : 0;
-}
-size_t conv_bytes(const og_engine* e)
-{
-    if (!e->conv_on()) return 0;
-    return sizeof(SnapConv) + ((size_t)(e->conv.cur ? e->conv.cur->K() : 0u) + (e->conv.old ? e->conv.old->K() : 0u) +
-                               conv_hist_frames(e) * e->cg->voice_channels) * 4;
-}
-
-// SamplePlayer: a section of its own at the very end -- the loaded samples' names and shapes in index order (the per-voice
-// words are state planes like any other); og_load_state resolves the names through the registry and loads them
-struct SnapSamples {
-    uint32_t magic, n;
-};
-struct SnapSample {
-    uint32_t name_len, frames, channels, reserved;
-};
-constexpr uint32_t SNAP_SMP_MAGIC = 0x504D534Fu; // "OSMP"
-// ... and, ONLY when a sample registered at a rate is loaded (a blob without one stays what it was), the section has another
-// magic and every entry is followed by the rates: og_load_state conforms again from the registry and compares
-struct SnapSampleRate {
-    uint32_t src_rate, rate, pool_frames, reserved; // src_rate 0: an untagged sample among tagged ones
-};
-constexpr uint32_t SNAP_SMPR_MAGIC = 0x524D534Fu; // "OSMR"
-bool samples_tagged(const og_engine* e)
-{
-    for (const auto& ls : e->samples)
-        if (ls.src_rate) return true;
-    return false;
-}
-size_t samples_bytes(const og_engine* e)
-{
-    if (e->cg->players.empty()) return 0;
-    size_t n = sizeof(SnapSamples);
-    const size_t extra = samples_tagged(e) ? sizeof(SnapSampleRate) : 0;
-    for (const auto& ls : e->samples) n += sizeof(SnapSample) + (ls.name.size() + 3) / 4 * 4 + extra;
-    return n;
-}
-
-size_t dsp_bytes(const og_engine* e)
-{
-    return (e->cg->state.size() + e->cg->lane_state.size() * e->cg->lpv * e->cg->lane_width) * (size_t)e->V * 4 +
-           (e->cg->bus_stage == ogc::BusStage::Tremolo ? 4 : 0) + e->ring_bytes();
-}
-// Every event that has not fired by frame_now.  Blocks that are still queued (og_set_bus_batching) consume the events
-// in [q_frame0, frame_now) when they are launched, and the snapshot header stores the post-queue frame_now: those
-// events must not be saved (they would fire a second time after a load -- ADVICE r2), so the horizon is frame_now,
-// not consumed_horizon().  og_save_state launches the queue first; og_state_bytes only counts.
-void collect_unconsumed(const og_engine* e, std::vector<SnapEvent>& out)
-{
-    const uint64_t hz = e->frame_now;
-    if (!e->seg_begin.empty()) {
-        std::vector<OgEvent> old;
-        for (uint32_t v = 0; v < e->V; ++v) {
-            old.clear();
-            e->old_events(v, old, hz); // the voice's segment, then its continuation
-            for (const OgEvent& ev : old) out.push_back(SnapEvent{v, ev.target, ev.frame, ev.value, 0u});
-        }
-    }
-    for (const HostEvent& h : e->pending)
-        if (h.frame >= hz) out.push_back(SnapEvent{h.voice, h.target, h.frame, h.value, h.block_local ? 1u : 0u});
-}
-// (a blob of an engine with grouped voices -- og_group_voices -- is version 3: the state planes and the events are in
-//  PHYSICAL order, and the logical -> physical table follows the events; loading it adopts the table)
-size_t control_bytes(const og_engine* e, size_t n_events, bool grouped)
-{
-    return sizeof(SnapHeader) + e->cg->inputs.size() * (sizeof(float) + sizeof(SnapRamp)) + n_events * sizeof(SnapEvent) +
-           (grouped ? (size_t)e->V * sizeof(uint32_t) : 0);
-}
-size_t control_bytes(const og_engine* e, size_t n_events) { return control_bytes(e, n_events, !e->phys_of.empty()); }
-} // namespace
-
-extern "C" {
-
-size_t og_state_bytes(const og_engine* e)
-{
-    return ogabi::guard_value<size_t>((size_t)0, [&]() -> size_t {
-    // (delay lines are part of the state: their size is known once og_init has sized them)
-    if (!e) return 0;
-    std::vector<SnapEvent> evs;
-    collect_unconsumed(e, evs);
-    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e);
-    });
-}
-
-int og_save_state(og_engine* e, void* dst, size_t cap)
-{
-    if (!e || !dst) return set_err(OG_E_INVALID, "null argument");
-    return guard([&] {
-        HIPCK(hipSetDevice(e->device));
-        e->flush_bus(); // queued blocks consume their events first: what is collected below is what frame_now has not reached
-        std::vector<SnapEvent> evs;
-        collect_unconsumed(e, evs);
-        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e)) throw std::runtime_error("buffer too small");
-        const size_t a = e->cg->state.size() * (size_t)e->V * 4, b = e->cg->lane_state.size() * (size_t)e->V * e->cg->lpv * e->cg->lane_width * 4;
-        e->bounce.d2h(dst, e->d_state, a, e->stream);
-        if (b) e->bounce.d2h((char*)dst + a, e->d_lane_state, b, e->stream);
-        if (e->d_bus_phase) HIPCK(hipMemcpyAsync((char*)dst + a + b, e->d_bus_phase, 4, hipMemcpyDeviceToHost, e->stream));
-        size_t off = a + b + (e->d_bus_phase ? 4 : 0);
-        for (size_t k = 0; k < e->cg->rings.size(); ++k) {
-            const size_t n = (size_t)e->ring_cap[k] * e->V * 4;
-            if (n) e->bounce.d2h((char*)dst + off, e->d_ring[k], n, e->stream);
-            off += n;
-        }
-        HIPCK(hipStreamSynchronize(e->stream));
-        char* p = (char*)dst + off;
-        const SnapHeader h{SNAP_MAGIC, e->phys_of.empty() ? 2u : 3u, e->frame_now, (uint32_t)e->cg->inputs.size(), e->active_ramps, (uint64_t)evs.size()};
-        memcpy(p, &h, sizeof h);
-        p += sizeof h;
-        memcpy(p, e->values.data(), e->values.size() * sizeof(float));
-        p += e->values.size() * sizeof(float);
-        for (const Ramp& r : e->ramps) {
-            const SnapRamp sr{r.current, r.target, r.increment, r.frames_remaining};
-            memcpy(p, &sr, sizeof sr);
-            p += sizeof sr;
-        }
-        if (!evs.empty()) memcpy(p, evs.data(), evs.size() * sizeof(SnapEvent));
-        p += evs.size() * sizeof(SnapEvent);
-        if (!e->phys_of.empty()) memcpy(p, e->phys_of.data(), (size_t)e->V * sizeof(uint32_t));
-        p += e->phys_of.empty() ? 0 : (size_t)e->V * sizeof(uint32_t);
-        if (e->conv_on()) {
-            const auto& cv = e->conv;
-            const uint32_t kc = cv.cur ? cv.cur->K() : 0u, ko = cv.old ? cv.old->K() : 0u;
-            const size_t hf = conv_hist_frames(e), vc = e->cg->voice_channels;
-            const SnapConv sc{SNAP_CONV_MAGIC, (uint32_t)vc, kc, cv.old ? ko : 0xFFFFFFFFu, cv.cur_from, cv.old_from, cv.fade_start, (uint32_t)hf, 0u};
-            memcpy(p, &sc, sizeof sc);
-            p += sizeof sc;
-            if (kc) memcpy(p, cv.cur->taps.data(), (size_t)kc * 4);
-            p += (size_t)kc * 4;
-            if (ko) memcpy(p, cv.old->taps.data(), (size_t)ko * 4);
-            p += (size_t)ko * 4;
-            if (hf) e->bounce.d2h(p, e->d_hist + (e->hist_pos - hf) * vc, hf * vc * 4, e->stream); // (hf <= hist_keep <= hist_pos)
-            p += hf * vc * 4;
-        }
-        if (!e->cg->players.empty()) {
-            const bool tagged = samples_tagged(e);
-            const SnapSamples sh{tagged ? SNAP_SMPR_MAGIC : SNAP_SMP_MAGIC, (uint32_t)e->samples.size()};
-            memcpy(p, &sh, sizeof sh);
-            p += sizeof sh;
-            for (const auto& ls : e->samples) {
-                const SnapSample ss{(uint32_t)ls.name.size(), ls.frames, ls.channels, 0u};
-                memcpy(p, &ss, sizeof ss);
-                p += sizeof ss;
-                const size_t padded = (ls.name.size() + 3) / 4 * 4;
-                memset(p, 0, padded);
-                memcpy(p, ls.name.data(), ls.name.size());
-                p += padded;
-                if (tagged) {
-                    const SnapSampleRate sr{ls.src_rate, ls.rate, ls.pool_frames, 0u};
-                    memcpy(p, &sr, sizeof sr);
-                    p += sizeof sr;
-                }
-            }
-        }
-        return OG_OK;
-    });
-}
-
-int og_load_state(og_engine* e, const void* src, size_t len)
-{
-    if (!e || !src) return set_err(OG_E_INVALID, "null argument");
-    const size_t dsp = dsp_bytes(e);
-    if (len < dsp + sizeof(SnapHeader)) return set_err(OG_E_INVALID, "state blob size mismatch");
-    SnapHeader h;
-    memcpy(&h, (const char*)src + dsp, sizeof h);
-    // (n_events is checked against the bytes that are there BEFORE it enters any size arithmetic: a crafted count must
-    //  not wrap control_bytes() around to a matching length)
-    const bool grouped = h.version == 3u;
-    const size_t fixed = control_bytes(e, 0, grouped);
-    if (h.magic != SNAP_MAGIC || (h.version != 2u && h.version != 3u) || h.n_inputs != e->cg->inputs.size() || len < dsp + fixed ||
-        h.n_events > (uint64_t)((len - dsp - fixed) / sizeof(SnapEvent)) || len < dsp + control_bytes(e, (size_t)h.n_events, grouped))
-        return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
-    size_t full_len = len;
-    len = dsp + control_bytes(e, (size_t)h.n_events, grouped); // what follows is the post-mix Convolver's section
-    // ... and, last, the SamplePlayer section: found from the front (behind the Convolver's, whose size its header gives)
-    struct WantSample {
-        std::string name;
-        uint32_t frames, channels;
-        uint32_t src_rate, rate, pool_frames;
-    };
-    std::vector<WantSample> want_samples;
-    if (!e->cg->players.empty()) {
-        const int rc = ogabi::guard([&]() -> int {
-            size_t at = len;
-            if (e->conv_on()) {
-                SnapConv pc{};
-                if (full_len - at < sizeof pc) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
-                memcpy(&pc, (const char*)src + at, sizeof pc);
-                const uint64_t ko = pc.k_old == 0xFFFFFFFFu ? 0u : pc.k_old;
-                const uint64_t n = sizeof pc + ((uint64_t)pc.k_cur + ko + (uint64_t)pc.hist_frames * pc.channels) * 4;
-                if (n > full_len - at) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
-                at += (size_t)n;
-            }
-            const size_t smp_at = at;
-            SnapSamples sh{};
-            bool ok = full_len - at >= sizeof sh;
-            if (ok) memcpy(&sh, (const char*)src + at, sizeof sh);
-            const bool tagged = ok && sh.magic == SNAP_SMPR_MAGIC;
-            ok = ok && (sh.magic == SNAP_SMP_MAGIC || tagged);
-            at += sizeof sh;
-            for (uint32_t i = 0; ok && i < sh.n; ++i) {
-                SnapSample ss{};
-                ok = full_len - at >= sizeof ss;
-                if (!ok) break;
-                memcpy(&ss, (const char*)src + at, sizeof ss);
-                at += sizeof ss;
-                const size_t padded = ((size_t)ss.name_len + 3) / 4 * 4;
-                ok = ss.name_len <= 4096u && full_len - at >= padded;
-                if (!ok) break;
-                want_samples.push_back({std::string((const char*)src + at, ss.name_len), ss.frames, ss.channels, 0u, 0u, ss.frames});
-                at += padded;
-                if (tagged) {
-                    SnapSampleRate sr{};
-                    ok = full_len - at >= sizeof sr;
-                    if (!ok) break;
-                    memcpy(&sr, (const char*)src + at, sizeof sr);
-                    at += sizeof sr;
-                    want_samples.back().src_rate = sr.src_rate;
-                    want_samples.back().rate = sr.rate;
-                    want_samples.back().pool_frames = sr.pool_frames;
-                }
-            }
-            if (!ok || at != full_len) return set_err(OG_E_INVALID, "state blob: the SamplePlayer section is missing or malformed");
-            // every sample must be there, in the shape it was saved with, before anything is changed
-            for (size_t i = 0; i < want_samples.size(); ++i) {
-                const WantSample& w = want_samples[i];
-                if (i < e->samples.size()) {
-                    const auto& ls = e->samples[i];
-                    if (ls.name != w.name || ls.frames != w.frames || ls.channels != w.channels || ls.src_rate != w.src_rate ||
-                        ls.pool_frames != w.pool_frames)
-                        return set_err(OG_E_INVALID, "state blob: sample " + std::to_string(i) + " is '" + w.name + "', this engine has loaded '" + ls.name + "' there");
-                    continue;
-                }
-                const auto sd = lookup_sample(w.name);
-                if (!sd) return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is not registered (og_register_sample)");
-                if (sd->frames != w.frames || sd->channels != w.channels)
-                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' is registered with another shape than the one it was saved with");
-                if (sd->rate != w.src_rate)
-                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' was saved at source rate " + std::to_string(w.src_rate) + ", it is registered at " + std::to_string(sd->rate) + " (0: no rate)");
-                if (sd->rate && (e->graph_rate("og_load_state") != w.rate ||
-                                 og_engine::conformed_frames(w.name, *sd, w.rate) != w.pool_frames))
-                    return set_err(OG_E_INVALID, "state blob: sample '" + w.name + "' was saved with " + std::to_string(w.pool_frames) + " frames conformed to " + std::to_string(w.rate) + " Hz; this engine's rate or the registered data give another length");
-            }
-            full_len = smp_at;
-            return OG_OK;
-        });
-        if (rc != OG_OK) return rc;
-    }
-    SnapConv sc{};
-    if (e->conv_on()) {
-        bool ok = full_len - len >= sizeof sc;
-        if (ok) memcpy(&sc, (const char*)src + len, sizeof sc);
-        ok = ok && sc.magic == SNAP_CONV_MAGIC && sc.channels == e->cg->voice_channels && sc.k_cur <= ogc::MAX_IR_TAPS &&
-             (sc.k_old == 0xFFFFFFFFu || sc.k_old <= ogc::MAX_IR_TAPS);
-        const uint64_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old, kmax = std::max<uint64_t>(sc.k_cur, ko);
-        ok = ok && sc.hist_frames == (kmax ? kmax - 1 : 0) &&
-             full_len - len == sizeof sc + ((size_t)sc.k_cur + ko + (size_t)sc.hist_frames * sc.channels) * 4;
-        if (!ok) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
-    } else if (full_len != len) {
-        return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
-    }
-    std::vector<uint32_t> new_phys, new_logical;
-    if (grouped) { // the voice order must be a permutation before anything is changed
-        new_phys.resize(e->V);
-        new_logical.assign(e->V, 0xFFFFFFFFu);
-        memcpy(new_phys.data(), (const char*)src + len - (size_t)e->V * sizeof(uint32_t), (size_t)e->V * sizeof(uint32_t));
-        for (uint32_t v = 0; v < e->V; ++v) {
-            if (new_phys[v] >= e->V || new_logical[new_phys[v]] != 0xFFFFFFFFu) return set_err(OG_E_INVALID, "state blob: the voice order is not a permutation");
-            new_logical[new_phys[v]] = v;
-        }
-    }
-    { // validate the events before anything is changed: the kernel indexes handlers / per-voice inputs by `target`
-        const char* q = (const char*)src + dsp + control_bytes(e, 0, false);
-        for (uint64_t i = 0; i < h.n_events; ++i, q += sizeof(SnapEvent)) {
-            SnapEvent ev;
-            memcpy(&ev, q, sizeof ev);
-            bool ok = ev.voice < e->V;
-            if (ev.target & OG_EV_SETVALUE) {
-                const uint32_t in = ev.target & ~OG_EV_SETVALUE;
-                ok = ok && in < e->cg->inputs.size() && e->cg->inputs[in].decl.kind == ogc::Kind::Value && e->cg->inputs[in].decl.per_voice;
-            } else {
-                ok = ok && (int)ev.target < e->cg->n_event_inputs;
-            }
-            if (!ok) return set_err(OG_E_INVALID, "state blob: event " + std::to_string(i) + " addresses a voice or input this graph does not have");
-        }
-    }
-    return guard([&] {
-        HIPCK(hipSetDevice(e->device));
-        e->flush_bus();
-        const size_t a = e->cg->state.size() * (size_t)e->V * 4, b = e->cg->lane_state.size() * (size_t)e->V * e->cg->lpv * e->cg->lane_width * 4;
-        e->bounce.h2d(e->d_state, src, a, e->stream);
-        if (b) e->bounce.h2d(e->d_lane_state, (const char*)src + a, b, e->stream);
-        if (e->d_bus_phase) HIPCK(hipMemcpyAsync(e->d_bus_phase, (const char*)src + a + b, 4, hipMemcpyHostToDevice, e->stream));
-        size_t off = a + b + (e->d_bus_phase ? 4 : 0);
-        for (size_t k = 0; k < e->cg->rings.size(); ++k) {
-            const size_t n = (size_t)e->ring_cap[k] * e->V * 4;
-            if (n) e->bounce.h2d(e->d_ring[k], (const char*)src + off, n, e->stream);
-            off += n;
-        }
-        e->reset_timeline();
-        HIPCK(hipStreamSynchronize(e->stream));
-        for (size_t i = e->samples.size(); i < want_samples.size(); ++i) { // (validated above; the registry may have changed since)
-            const auto sd = lookup_sample(want_samples[i].name);
-            if (!sd || sd->frames != want_samples[i].frames || sd->channels != want_samples[i].channels || sd->rate != want_samples[i].src_rate)
-                throw ogabi::Error(OG_E_INVALID, "state blob: sample '" + want_samples[i].name + "' is not registered in the shape it was saved with");
-            (void)e->load_sample(want_samples[i].name, *sd);
-        }
-        if (e->conv_on()) {
-            const size_t vc = e->cg->voice_channels;
-            const size_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old;
-            const float* q = (const float*)((const char*)src + len + sizeof sc);
-            if (sc.hist_frames > e->hist_keep) e->conv_alloc(sc.hist_frames);
-            e->conv.cur = e->conv_upload(q, sc.k_cur);
-            e->conv.old = sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + sc.k_cur, ko);
-            e->conv.cur_from = sc.cur_from;
-            e->conv.old_from = sc.old_from;
-            e->conv.fade_start = sc.fade_start;
-            e->conv_pending.reset();
-            HIPCK(hipMemsetAsync(e->d_hist, 0, e->hist_len * vc * 4, e->stream));
-            e->hist_pos = e->hist_keep;
-            if (sc.hist_frames)
-                e->bounce.h2d(e->d_hist + (e->hist_pos - sc.hist_frames) * vc, q + sc.k_cur + ko, (size_t)sc.hist_frames * vc * 4, e->stream);
-            HIPCK(hipStreamSynchronize(e->stream));
-            e->conv_gc();
-        }
-        const bool order_changed = e->phys_of != new_phys;
-        e->phys_of.swap(new_phys); // (version 2: identity)
-        e->logical_of.swap(new_logical);
-        if (order_changed && e->n_taps) { // taps were resolved to physical slots under the old order: resolve the SAME voices again
-            std::vector<int32_t> slot(e->V, -1);
-            for (uint32_t i = 0; i < e->n_taps; ++i) slot[e->phys(e->tap_voices[i])] = (int32_t)i;
-            e->bounce.h2d(e->d_tap_slot, slot.data(), (size_t)e->V * 4, e->stream);
-            HIPCK(hipStreamSynchronize(e->stream));
-        }
-        const char* p = (const char*)src + off + sizeof h;
-        memcpy(e->values.data(), p, e->values.size() * sizeof(float));
-        p += e->values.size() * sizeof(float);
-        for (Ramp& r : e->ramps) {
-            SnapRamp sr;
-            memcpy(&sr, p, sizeof sr);
-            p += sizeof sr;
-            r.current = sr.current;
-            r.target = sr.target;
-            r.increment = sr.increment;
-            r.frames_remaining = sr.frames_remaining;
-        }
-        e->active_ramps = h.active_ramps;
-        e->frame_now = h.frame_now;
-        for (uint64_t i = 0; i < h.n_events; ++i) {
-            SnapEvent ev;
-            memcpy(&ev, p, sizeof ev);
-            p += sizeof ev;
-            const bool local = ev.block_local != 0u;
-            e->pending.push_back(HostEvent{ev.voice, std::max(ev.frame, h.frame_now), ev.target, ev.value, e->seq++, local});
-            if (local) {
-                e->n_block_local += 1;
-                if (!(ev.target & OG_EV_SETVALUE)) { // the try_push capacity count of the block being assembled
-                    const size_t ne = (size_t)std::max(1, e->cg->n_event_inputs);
-                    if (e->local_cnt.empty()) e->local_cnt.assign((size_t)e->V * ne, 0);
-                    const size_t k = (size_t)ev.voice * ne + ev.target;
-                    if (e->local_cnt[k] == 0) e->local_touched.push_back((uint32_t)k);
-                    if (e->local_cnt[k] < 255) e->local_cnt[k] += 1;
-                }
-            }
-        }
-        return OG_OK;
-    });
-}
-
-} // extern "C"
-
-#include "og_cluster.inl"

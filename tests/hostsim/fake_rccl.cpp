@@ -1,4 +1,4 @@
-// tests/hostsim/fake_rccl.cpp -- TEST INFRASTRUCTURE: the six RCCL entry points og_cluster.inl binds with dlopen, for the
+// tests/hostsim/fake_rccl.cpp -- TEST INFRASTRUCTURE: the six RCCL entry points og_cluster.cpp binds with dlopen, for the
 // host simulator, where every "device" is host memory of one process.  Built as _build/fake_rccl/librccl.so.1; the test
 // process finds it before the real library through LD_LIBRARY_PATH.  ncclReduce inside a group is recorded and executed at
 // ncclGroupEnd: root's recvbuf = sum over the ranks' sendbufs in rank order (float32 sum is all the cluster uses).

@@ -1,4 +1,4 @@
-// tests/hostsim/rccl/rccl.h -- TEST INFRASTRUCTURE: the RCCL types og_cluster.inl names (the library binds RCCL with dlopen,
+// tests/hostsim/rccl/rccl.h -- TEST INFRASTRUCTURE: the RCCL types og_cluster.cpp names (the library binds RCCL with dlopen,
 // and only when a cluster spans more than one device -- which the host simulator never reports).
 #pragma once
 #include <hip/hip_runtime.h>

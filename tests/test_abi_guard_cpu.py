@@ -7,7 +7,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "oscen_amd", "csrc")
-SOURCES = ["og_engine.cpp", "og_cluster.inl", "og_midi.cpp", "og_wav.cpp", "og_dsl.cpp", "og_graph.cpp", "og_builtin.cpp", "og_jit.cpp"]
+SOURCES = ["og_engine.cpp", "og_snapshot.cpp", "og_cluster.cpp", "og_midi.cpp", "og_wav.cpp", "og_dsl.cpp", "og_graph.cpp", "og_builtin.cpp", "og_jit.cpp"]
 # what makes a body able to throw: allocation, containers, strings, the compiler, explicit throws
 RISKY = ["new ", "std::", "push_back", "resize", "emplace", ".assign(", "throw", "compile(", "make_unique", "HIPCK"]
 
@@ -48,8 +48,8 @@ def test_guard_maps_exception_types_to_codes_without_reading_messages():
     guard = abi[abi.index("int guard(F&& f) noexcept"):abi.index("template <class T, class F>")]
     assert "e.code" in guard and "std::bad_alloc" in guard and "catch (...)" in guard
     assert ".find(" not in guard  # (round 3 classified errors by substrings of the message)
-    eng = open(os.path.join(CSRC, "og_engine.cpp")).read()
-    assert 'm.find("not supported")' not in eng
+    for f in ("og_engine.cpp", "og_engine.h", "og_snapshot.cpp", "og_cluster.cpp"):
+        assert 'm.find("not supported")' not in open(os.path.join(CSRC, f)).read(), f
 
 
 def test_environment_knobs_are_not_read_on_the_block_path():

@@ -144,7 +144,7 @@ def test_load_state_rejects_crafted_event_records():
     eng.process_block(64)
     blob = eng.save_state()
     eng.load_state(blob)  # the honest blob loads
-    # layout of the control block (og_engine.cpp): header {magic, version, frame_now u64, n_inputs, active_ramps,
+    # layout of the control block (og_snapshot.cpp): header {magic, version, frame_now u64, n_inputs, active_ramps,
     # n_events u64}, values, ramps, then 24-byte event records {voice, target, frame u64, value, block_local}
     n_inputs = eng.lib.og_num_inputs(eng.h)
     ctrl = blob.nbytes - (32 + n_inputs * (4 + 16) + 2 * 24)

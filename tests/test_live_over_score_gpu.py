@@ -5,7 +5,7 @@ The reference merges the events staged for a block into it by `frame_offset`, bl
 Here a whole score can be resident on the device (`og_schedule_*`); until round 6 a live push re-wrote the voice's remaining
 score.  Now the push becomes a short segment {what is due up to the end of the launch being prepared, the push}; the
 rest of the score stays where it lies as the voice's continuation, and the engine points the voice at it -- a cursor
-update -- before the launch in which its first event is due (og_engine.cpp, merge_voice).  Checked: the samples against the oracle fed the merged event list, the same engine with the whole list
+update -- before the launch in which its first event is due (og_timeline.h, merge_voice).  Checked: the samples against the oracle fed the merged event list, the same engine with the whole list
 scheduled up front bit for bit, and `og_events_copied` -- the cost of the live messages does not grow with the score."""
 import numpy as np
 import pytest
@@ -94,7 +94,7 @@ def test_live_messages_cut_into_a_resident_score_without_rewriting_it(split, mon
     st = e_live.event_stats
     assert st["full_rebuilds"] == 1 and st["incremental_updates"] >= blocks - 4, st
     # the cost of the live path: every message carries over at most what was due in its own block --
-    # not the ~500 events its voice still has to play (a rest below 64 events would be carried over: og_engine.cpp, CONT_MIN)
+    # not the ~500 events its voice still has to play (a rest below 64 events would be carried over: og_timeline.h, CONT_MIN)
     assert st["events_copied"] <= len(live) * 12, (st, len(live), per_voice)
 
     # the same timeline scheduled up front, one segment per voice, no continuation anywhere: bit for bit
