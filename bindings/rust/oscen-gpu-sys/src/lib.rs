@@ -56,6 +56,11 @@ extern "C" {
     pub fn og_graph_add_bus_convolver(g: *mut og_graph_desc, name: *const c_char, ir_name: *const c_char) -> c_int;
     pub fn og_register_ir(name: *const c_char, taps: *const c_float, n_taps: u32) -> c_int;
     pub fn og_unregister_ir(name: *const c_char) -> c_int;
+    pub fn og_register_ir_asset(name: *const c_char, interleaved: *const c_float, frames: u64, channels: u32, sample_rate: u32) -> c_int;
+    pub fn og_register_ir_wav(name: *const c_char, path: *const c_char) -> c_int;
+    pub fn og_ir_info(name: *const c_char, frames: *mut u64, channels: *mut u32, sample_rate: *mut u32) -> c_int;
+    pub fn og_bus_ir_info(e: *const og_engine, taps: *mut u32, channels: *mut u32) -> c_int;
+    pub fn og_read_bus_ir(e: *const og_engine, channel: u32, out: *mut c_float, capacity: u32) -> c_int;
     pub fn og_set_bus_ir(e: *mut og_engine, ir_name: *const c_char) -> c_int;
     pub fn og_graph_connect_via(g: *mut og_graph_desc, src: *const c_char, via: *const c_char,
                                 dst: *const c_char) -> c_int;

@@ -219,7 +219,49 @@ pub fn register_function(name: &str, args: &[(&str, u32)], result_channels: u32,
     ck(unsafe { sys::og_register_function(&f) }).map(|_| ())
 }
 
+/// An impulse response as an ASSET (the reference's `external ir: AudioAsset; ir -> reverb.ir;`): `channels` (1..8)
+/// interleaved channels at `sample_rate`.  `GpuGraph::set_bus_ir` conforms it to the engine's rate and maps its channels
+/// onto the bus's, as ConvolverConsumer::build does.
+pub fn register_ir_asset(name: &str, interleaved: &[f32], channels: u32, sample_rate: u32) -> Result<(), GpuError> {
+    let c_name = CString::new(name).unwrap();
+    if channels == 0 || interleaved.len() % channels as usize != 0 { // (refused here, where the slice's length is still known)
+        return Err(GpuError(-1, format!("register_ir_asset: {} samples are not whole frames of {} channels", interleaved.len(), channels)));
+    }
+    let frames = interleaved.len() as u64 / channels as u64;
+    ck(unsafe { sys::og_register_ir_asset(c_name.as_ptr(), interleaved.as_ptr(), frames, channels, sample_rate) }).map(|_| ())
+}
+/// `graph.ir.load_wav(path)`: the file (PCM 16 / 24 / 32, float 32) as an asset response at the header's rate
+pub fn register_ir_wav(name: &str, path: &str) -> Result<(), GpuError> {
+    let (c_name, c_path) = (CString::new(name).unwrap(), CString::new(path).unwrap());
+    ck(unsafe { sys::og_register_ir_wav(c_name.as_ptr(), c_path.as_ptr()) }).map(|_| ())
+}
+/// (frames, channels, sample rate) of a registered response; rate 0: the mono, session-rate form
+pub fn ir_info(name: &str) -> Result<(u64, u32, u32), GpuError> {
+    let c_name = CString::new(name).unwrap();
+    let (mut frames, mut channels, mut rate) = (0u64, 0u32, 0u32);
+    ck(unsafe { sys::og_ir_info(c_name.as_ptr(), &mut frames, &mut channels, &mut rate) })?;
+    Ok((frames, channels, rate))
+}
+
 impl<const IN: usize> GpuGraph<IN> {
+    /// publish a registered response on the post-mix Convolver from the next block on, with the 20 ms equal-power crossfade
+    pub fn set_bus_ir(&mut self, name: &str) -> Result<(), GpuError> {
+        let c_name = CString::new(name).unwrap();
+        ck(unsafe { sys::og_set_bus_ir(self.e, c_name.as_ptr()) }).map(|_| ())
+    }
+    /// the response published last as the kernels read it: one Vec of taps per tap plane (one plane: shared by every channel)
+    pub fn bus_ir(&self) -> Result<Vec<Vec<f32>>, GpuError> {
+        let (mut taps, mut planes) = (0u32, 0u32);
+        ck(unsafe { sys::og_bus_ir_info(self.e, &mut taps, &mut planes) })?;
+        let mut out = Vec::new();
+        for c in 0..planes {
+            let mut plane = vec![0.0f32; taps.max(1) as usize];
+            ck(unsafe { sys::og_read_bus_ir(self.e, c, plane.as_mut_ptr(), taps) })?;
+            plane.truncate(taps as usize);
+            out.push(plane);
+        }
+        Ok(out)
+    }
     /// `graph.<node>.<field>` of every voice in `first_voice .. first_voice + n` (the generated struct's node fields are
     /// public in the reference; here a node's persistent fields are planes of the state image): "node.field",
     /// "array[i].field", "nested.node.field"

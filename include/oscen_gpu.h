@@ -174,11 +174,27 @@ int og_graph_add_bus_node(og_graph_desc* g, const char* name, const char* type_c
  * segment; parentheses and arguments are ignored.  Mono, at the session rate, copied; a name that exists is replaced;
  * n_taps == 0 is legal (silence); at most 2^20 taps. */
 int og_register_ir(const char* name, const float* taps, uint32_t n_taps);
+/* The ASSET form of a response, in the same name space (the reference's `#[input(asset)] ir` slot of Convolver<F>: an
+ * AudioAsset handed to ConvolverConsumer::build): 1..8 channels of interleaved frames at their own rate, copied; frames *
+ * channels at most 2^28.  sample_rate == 0 and frames == 0 are OG_E_INVALID (AudioAsset::from_samples' checks).  A name that
+ * exists, in either form, is replaced; the name rules are og_register_ir's.  An asset response is PUBLISHED with
+ * og_set_bus_ir, which conforms it to the engine's rate and maps its channels onto the bus's; `Convolver::with_ir(name())`
+ * -- the reference's mono, session-rate constructor -- and og_graph_add_bus_convolver with its name refuse it
+ * (OG_E_INVALID): build the node with ir_name == NULL and publish. */
+int og_register_ir_asset(const char* name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t sample_rate);
+/* Reads a RIFF/WAVE file with og_register_sample_wav's reader (PCM 16 / 24 / 32, IEEE float 32, plain or extensible; anything
+ * else OG_E_UNSUPPORTED, malformed OG_E_INVALID) and registers it as an asset response at the header's rate. */
+int og_register_ir_wav(const char* name, const char* path);
+/* What a name holds: frames (taps), channels and rate -- 1 channel and rate 0 for a response registered through
+ * og_register_ir.  Out-pointers may be NULL. */
+int og_ir_info(const char* name, uint64_t* frames, uint32_t* channels, uint32_t* sample_rate);
+/* Removes a response of either form. */
 int og_unregister_ir(const char* name);
 /* The post-mix Convolver (oscen-lib/src/convolution/mod.rs: the sample-exact full convolution, zero latency) on the summed
  * voices: `name = Convolver::with_ir(ir_name())`, or, ir_name == NULL, `Convolver::new()` -- silent until og_set_bus_ir.
  * Wired like the Tremolo: "<voice output name>" -> "name.input", "name.output" -> "<second graph output>".  The output has
- * the channels of the voices (Frame<2> voices: the mono response on both channels).  One bus node per graph; a Convolver
+ * the channels of the voices (Frame<2> voices: the mono response on both channels; a multi-channel asset response published
+ * with og_set_bus_ir: one response per channel).  One bus node per graph; a Convolver
  * anywhere else (inside a voice graph, oversampled, in a feedback path) and a cluster over such a graph are
  * OG_E_UNSUPPORTED. */
 int og_graph_add_bus_convolver(og_graph_desc* g, const char* name, const char* ir_name);
@@ -281,7 +297,7 @@ int og_register_sample_wav(const char* name, const char* path);
 int og_sample_info(const char* name, uint64_t* frames, uint32_t* channels, uint32_t* sample_rate);
 int og_read_sample(const char* name, float* out, uint64_t capacity_frames);
 /* The resampler by itself, on the current device, host buffers in and out -- e.g. to conform an impulse response before
- * og_register_ir (the IR registry carries no rates).  og_resample_frames gives the output length, round(frames * dst / src);
+ * og_register_ir (whose mono form carries no rate; og_register_ir_asset does, and og_set_bus_ir conforms it).  og_resample_frames gives the output length, round(frames * dst / src);
  * og_resample writes that many interleaved frames (OG_E_INVALID when out_capacity_frames is smaller).  Equal rates copy the
  * input.  1..8 channels, frames >= 1, both rates > 0. */
 int og_resample_frames(uint64_t frames, uint32_t src_rate, uint32_t dst_rate, uint64_t* out_frames);
@@ -421,8 +437,26 @@ int og_post_mix_kind(const og_engine* e);
  * crossfade (convolution/mod.rs:535-573): the new response starts on empty history, the old one keeps running for
  * fade_len = max(1, round(0.02 sr)) samples, out = new sin(g pi/2) + old cos(g pi/2), g = pos / fade_len; a second swap
  * during a fade drops the fading-out response at once.  og_init clears history and fade.  Allocates: not for the audio
- * thread.  OG_E_INVALID on an engine without a post-mix Convolver or for an unregistered name. */
+ * thread.  OG_E_INVALID on an engine without a post-mix Convolver or for an unregistered name.
+ * An ASSET response (og_register_ir_asset / og_register_ir_wav) is first made playable, off the audio path and before
+ * anything of the engine changes (ConvolverConsumer::build, convolution/mod.rs:335-351, 407-411):
+ *  - conformed: og_init comes first, and the engine's rate must be a positive integer (an asset's rate is one) -- on any other
+ *    engine an asset is OG_E_INVALID, even one that would only be copied; a rate other than the engine's sends EVERY source channel through the load
+ *    path's resampler on the device -- og_resample_frames taps, bit for bit what og_resample returns; equal rates copy;
+ *  - mapped onto the bus's C channels: C == 1 and several source channels: their average (AudioAsset::to_mono: channels
+ *    0, 1, .. added in that order into 0.0f, times 1.0f / channels, in f32); one source channel: ONE tap plane shared by all
+ *    bus channels (the mono path, no extra memory); otherwise bus channel c takes source channel min(c, channels - 1);
+ *  - limited: more than 2^20 conformed taps per channel is OG_E_UNSUPPORTED and the engine is untouched.
+ * The swap is the one above, whatever the forms of the two responses.  og_init at ANOTHER rate keeps the published taps as
+ * they are (the reference's prepare() rebuilds from the stored IR, "taken to be at session rate"): publish again to conform
+ * to the new rate.  Waits for the device. */
 int og_set_bus_ir(og_engine* e, const char* ir_name);
+/* The response published last (the swap waiting for the next block, else the current one), as the kernels read it:
+ * its taps per channel and its tap planes -- channels == 1: one plane shared by every bus channel, otherwise one per bus
+ * channel.  og_read_bus_ir copies the taps bus channel `channel` (< og_voice_channels) is convolved with; OG_E_INVALID when
+ * capacity (in taps) is smaller. */
+int og_bus_ir_info(const og_engine* e, uint32_t* taps, uint32_t* channels);
+int og_read_bus_ir(const og_engine* e, uint32_t channel, float* out, uint32_t capacity);
 uint64_t og_frames_processed(const og_engine* e);
 /* layout facts used by the roofline accounting */
 uint32_t og_state_words_per_voice(const og_engine* e);

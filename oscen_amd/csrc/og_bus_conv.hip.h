@@ -9,6 +9,10 @@
 //                      tile i, the products of taps [j S, (j+1) S) of channel c -- taps and the input window
 //                      (OG_CONV_F + OG_CONV_S samples) staged in LDS, four consecutive frames per lane, accumulated with
 //                      fmaf in registers in ASCENDING k -- and writes one partial row per segment.
+//                      A response is either ONE tap plane shared by every channel (tap_stride == 0: the mono response of
+//                      og_register_ir, or a one-channel asset) or one plane per channel, tap_stride floats apart (a
+//                      multi-channel asset, MultiConvolverEngine::from_asset): workgroup (i, j, c) stages taps + c * tap_stride.
+//                      The offset is uniform over the workgroup and paid once, in front of the staging loop.
 //   og_bus_conv_finish sums the rows of a frame in a fixed order (four interleaved accumulators over the segment number,
 //                      folded (a0 + a1) + (a2 + a3)), applies the equal-power crossfade of a live response swap and writes
 //                      the wet bus.
@@ -39,10 +43,11 @@
 #define OG_CONV_MAX_TAPS (1u << 20) // 4 096 partial rows per frame at most
 
 struct OgConvResponse {
-    const float* taps; // device, n_taps floats
-    uint32_t n_taps;
+    const float* taps; // device: n_taps floats, or -- tap_stride != 0 -- one plane of n_taps floats per channel, tap_stride apart
+    uint32_t n_taps;   // per channel
     uint32_t n_frames; // frames of the run this response is evaluated for (the fading-out one: up to the end of the fade)
     int32_t lo;        // first readable sample, relative to the run's first frame: max(history valid from, start of the buffer)
+    uint32_t tap_stride; // floats between the tap planes of two channels; 0: every channel reads the same plane
     float* rows;       // partial rows [segment][channel][row_stride]
 };
 
@@ -63,7 +68,8 @@ __global__ __launch_bounds__(OG_CONV_LANES) void og_bus_conv(const float* __rest
         const int32_t f = w0 + (int32_t)j;
         wf[j] = (f >= r.lo && f < (int32_t)r.n_frames) ? x[(int64_t)f * (int64_t)channels + c] : 0.0f;
     }
-    for (uint32_t j = lane; j < OG_CONV_S; j += OG_CONV_LANES) tf[j] = (k0 + j < r.n_taps) ? r.taps[k0 + j] : 0.0f;
+    const float* __restrict__ taps = r.taps + (size_t)c * r.tap_stride;
+    for (uint32_t j = lane; j < OG_CONV_S; j += OG_CONV_LANES) tf[j] = (k0 + j < r.n_taps) ? taps[k0 + j] : 0.0f;
     __syncthreads();
     const uint32_t seg_taps = min((uint32_t)OG_CONV_S, r.n_taps - k0);
     float y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
@@ -135,6 +141,31 @@ __global__ __launch_bounds__(256) void og_bus_conv_finish(OgConvResponse cur, Og
         y = y * gain_new + o * gain_old;
     }
     out[(size_t)f * channels + c] = y;
+}
+
+// og_set_bus_ir on an asset response: the conformed frames [n_taps][src_ch] (interleaved) -> tap planes [gridDim.y][n_taps],
+// with the channel mapping of MultiConvolverEngine::from_asset (convolution/mod.rs:335-351).  downmix (a multi-channel
+// response on a mono bus, AudioAsset::to_mono, asset/mod.rs:115-131): channels 0, 1, .. added in that order into 0.0f, then
+// times inv = 1.0f / src_ch (formed on the host) -- that order in f32 is the contract.  Otherwise plane p takes source
+// channel min(p, src_ch - 1).
+OG_HD float og_bus_ir_tap(const float* __restrict__ frame, uint32_t src_ch, uint32_t p, uint32_t downmix, float inv)
+{
+    if (downmix) {
+        float acc = 0.0f;
+        for (uint32_t c = 0; c < src_ch; ++c) acc += frame[c];
+        return acc * inv;
+    }
+    return frame[p < src_ch - 1u ? p : src_ch - 1u];
+}
+
+// one lane per tap of a plane
+__global__ __launch_bounds__(256) void og_bus_ir_planes(const float* __restrict__ conformed, uint32_t n_taps, uint32_t src_ch, uint32_t downmix,
+                                                        float inv, float* __restrict__ dst)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t p = blockIdx.y;
+    if (k >= n_taps) return;
+    dst[(size_t)p * n_taps + k] = og_bus_ir_tap(conformed + (size_t)k * src_ch, src_ch, p, downmix, inv);
 }
 
 // history upkeep: dst[i] = src[i] (the newest samples moved to the front of the buffer; the ranges never overlap)

@@ -273,6 +273,39 @@ void og_engine::conv_alloc(size_t need_hist)
     HIPCK(hipStreamSynchronize(stream));
 }
 
+// og_set_bus_ir on an asset response (ConvolverConsumer::build -> MultiConvolverEngine::from_asset, convolution/mod.rs:335-351):
+// every source channel conformed to the engine's rate by the load path's resampler (equal rates: as registered), then mapped
+// onto the bus's channels -- a multi-channel response on a mono bus is averaged (to_mono), one source channel is ONE plane
+// shared by every bus channel, otherwise bus channel c takes source channel min(c, channels - 1).  Every check comes before
+// the device is touched; the engine's state is not changed here.  Waits for the stream (the host copy comes back).
+std::shared_ptr<og_engine::ConvIR> og_engine::conv_build_asset(const std::string& name, const ogc::IrAsset& a)
+{
+    const uint32_t rate = graph_rate("og_set_bus_ir");
+    const bool conform = a.rate != rate;
+    const OgResamplePlan plan = conform ? og_resample_plan(a.frames, a.rate, rate) : OgResamplePlan{};
+    const uint64_t K = conform ? plan.out_len : a.frames;
+    if (K > OG_CONV_MAX_TAPS)
+        throw ogabi::Unsupported("impulse response '" + name + "' (" + std::to_string(a.frames) + " frames at " + std::to_string(a.rate) + " Hz) has " +
+                                 std::to_string(K) + " taps per channel once conformed to " + std::to_string(rate) + " Hz (at most " + std::to_string(OG_CONV_MAX_TAPS) + ")");
+    if (K == 0)
+        throw ogabi::Error(OG_E_INVALID, "impulse response '" + name + "' (" + std::to_string(a.frames) + " frames at " + std::to_string(a.rate) + " Hz) is empty once conformed to " + std::to_string(rate) + " Hz");
+    const uint32_t vc = cg->voice_channels;
+    const bool downmix = vc == 1 && a.channels > 1;
+    auto ir = std::make_shared<ConvIR>();
+    ir->planes = (a.channels == 1 || vc == 1) ? 1u : vc;
+    ir->taps.resize((size_t)ir->planes * K);
+    DeviceScratch d_src(a.interleaved.size()), d_conf(conform ? (size_t)K * a.channels : 1);
+    bounce.h2d(d_src.p, a.interleaved.data(), a.interleaved.size() * 4, stream);
+    if (conform) og_resample_launch(d_src.p, a.frames, a.channels, plan, d_conf.p, stream);
+    HIPCK(hipMalloc(&ir->d, ir->taps.size() * 4));
+    conv_bufs.push_back(ir->d);
+    hipLaunchKernelGGL(og_bus_ir_planes, dim3((unsigned)((K + 255) / 256), ir->planes), dim3(256), 0, stream, conform ? d_conf.p : d_src.p, (uint32_t)K,
+                       a.channels, downmix ? 1u : 0u, 1.0f / (float)a.channels, ir->d);
+    HIPCK(hipGetLastError());
+    bounce.d2h(ir->taps.data(), ir->d, ir->taps.size() * 4, stream);
+    return ir;
+}
+
 // the length a tagged sample has once conformed to `dst` (the checks of from_samples behind the resample)
 uint32_t og_engine::conformed_frames(const std::string& name, const SampleData& sd, uint32_t dst)
 {
@@ -776,6 +809,7 @@ void og_engine::flush_bus()
                 r.n_taps = ir ? ir->K() : 0u;
                 r.n_frames = frames;
                 r.lo = (int32_t)std::max<int64_t>(buf_lo, from >= t0 ? (int64_t)std::min<uint64_t>(from - t0, 0x7fffffffu) : -(int64_t)std::min<uint64_t>(t0 - from, 0x7fffffffu));
+                r.tap_stride = ir ? ir->stride() : 0u;
                 r.rows = rows;
                 return r;
             };
@@ -1080,6 +1114,30 @@ int og_register_ir(const char* name, const float* taps, uint32_t n_taps)
     return ogabi::guard([&]() -> int {
     if (!name || (n_taps && !taps)) return set_err(OG_E_INVALID, "null argument");
     ogc::register_ir(name, taps, n_taps);
+    return OG_OK;
+    });
+}
+
+// the asset form: every check on the data is ogc::register_ir_asset's (one copy, the one the stand-alone program runs)
+int og_register_ir_asset(const char* name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t sample_rate)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name) return set_err(OG_E_INVALID, "null argument");
+    ogc::register_ir_asset(name, interleaved, frames, channels, sample_rate);
+    return OG_OK;
+    });
+}
+
+int og_ir_info(const char* name, uint64_t* frames, uint32_t* channels, uint32_t* sample_rate)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name) return set_err(OG_E_INVALID, "null argument");
+    std::string resolved;
+    const ogc::IrEntry ir = ogc::lookup_ir_entry(name, &resolved);
+    if (!ir) return set_err(OG_E_INVALID, "no impulse response '" + resolved + "'");
+    if (frames) *frames = ir.asset ? ir.asset->frames : ir.taps->size();
+    if (channels) *channels = ir.asset ? ir.asset->channels : 1u;
+    if (sample_rate) *sample_rate = ir.asset ? ir.asset->rate : 0u;
     return OG_OK;
     });
 }
@@ -1440,17 +1498,55 @@ int og_set_bus_ir(og_engine* e, const char* ir_name)
     return guard([&]() -> int {
         if (!e->conv_on()) return set_err(OG_E_INVALID, "og_set_bus_ir: this engine has no post-mix Convolver");
         std::string resolved;
-        const auto taps = ogc::lookup_ir(ir_name, &resolved);
-        if (!taps) return set_err(OG_E_INVALID, "unknown impulse response '" + resolved + "'; responses are registered with og_register_ir");
+        const ogc::IrEntry ir = ogc::lookup_ir_entry(ir_name, &resolved);
+        if (!ir) return set_err(OG_E_INVALID, "unknown impulse response '" + resolved + "'; responses are registered with og_register_ir, og_register_ir_asset or og_register_ir_wav");
         HIPCK(hipSetDevice(e->device));
-        if (taps->size() > e->hist_keep + 1) { // a longer response than the buffers were sized for (not a real-time path)
+        // an asset response: the playable form is built first -- nothing of the engine has changed if that is refused
+        std::shared_ptr<og_engine::ConvIR> built;
+        if (ir.asset) built = e->conv_build_asset(resolved, *ir.asset);
+        const size_t k = built ? built->K() : ir.taps->size();
+        if (k > e->hist_keep + 1) { // a longer response than the buffers were sized for (not a real-time path)
             e->flush_bus();
             HIPCK(hipStreamSynchronize(e->stream));
-            e->conv_alloc(taps->size());
+            e->conv_alloc(k);
         }
+        // the new response replaces a swap no block has picked up yet: that one goes before conv_gc (no launch ever read
+        // it), an asset's planes are already held by `built` when the gc runs
+        e->conv_pending = built;
         e->conv_gc();
-        e->conv_pending = e->conv_upload(taps->data(), taps->size()); // replaces a swap no block has picked up yet
+        if (!built) e->conv_pending = e->conv_upload(ir.taps->data(), ir.taps->size());
         return OG_OK;
+    });
+}
+
+namespace {
+// the response og_set_bus_ir published last: the swap waiting for the next block, else the one the last block ran under
+const og_engine::ConvIR* published_ir(const og_engine* e) { return e->conv_pending ? e->conv_pending.get() : e->conv.cur.get(); }
+} // namespace
+
+int og_bus_ir_info(const og_engine* e, uint32_t* taps, uint32_t* channels)
+{
+    return ogabi::guard([&]() -> int {
+    if (!e) return set_err(OG_E_INVALID, "null argument");
+    if (!e->conv_on()) return set_err(OG_E_INVALID, "og_bus_ir_info: this engine has no post-mix Convolver");
+    const og_engine::ConvIR* ir = published_ir(e);
+    if (taps) *taps = ir ? ir->K() : 0u;
+    if (channels) *channels = ir ? ir->planes : 1u;
+    return OG_OK;
+    });
+}
+
+int og_read_bus_ir(const og_engine* e, uint32_t channel, float* out, uint32_t capacity)
+{
+    return ogabi::guard([&]() -> int {
+    if (!e || !out) return set_err(OG_E_INVALID, "null argument");
+    if (!e->conv_on()) return set_err(OG_E_INVALID, "og_read_bus_ir: this engine has no post-mix Convolver");
+    if (channel >= e->cg->voice_channels) return set_err(OG_E_INVALID, "og_read_bus_ir: the bus has " + std::to_string(e->cg->voice_channels) + " channels");
+    const og_engine::ConvIR* ir = published_ir(e);
+    const uint32_t k = ir ? ir->K() : 0u;
+    if (capacity < k) return set_err(OG_E_INVALID, "og_read_bus_ir: the output holds " + std::to_string(capacity) + " taps, the response has " + std::to_string(k));
+    if (k) memcpy(out, ir->taps.data() + (size_t)(ir->planes > 1 ? channel : 0u) * k, (size_t)k * 4);
+    return OG_OK;
     });
 }
 

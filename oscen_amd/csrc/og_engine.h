@@ -249,10 +249,14 @@ struct og_engine {
     // ---- post-mix Convolver (og_bus_conv.hip.h) ---------------------------------------------------
     // A response lives on the device from og_set_bus_ir (or og_create) until the engine is destroyed or a later
     // og_set_bus_ir finds the stream idle: launches already queued may still read it.
+    // planes == 1: one tap plane shared by every bus channel (a mono response, a one-channel asset, any asset on a mono bus);
+    // otherwise one plane per bus channel, K() floats apart, plane-major on the device and in the host copy
     struct ConvIR {
         float* d = nullptr;
-        std::vector<float> taps; // host copy (snapshots)
-        uint32_t K() const { return (uint32_t)taps.size(); }
+        std::vector<float> taps; // host copy (snapshots, og_read_bus_ir): [planes][K]
+        uint32_t planes = 1;
+        uint32_t K() const { return (uint32_t)(taps.size() / planes); }
+        uint32_t stride() const { return planes > 1 ? K() : 0u; } // OgConvResponse::tap_stride
     };
     // what a block is rendered under: the current response and, during the crossfade of a swap, the outgoing one; each with
     // the frame its history is valid from (a new response only sees input from the swap frame on)
@@ -277,17 +281,20 @@ struct og_engine {
     size_t conv_rows_half = 0;
     bool conv_on() const { return cg->bus_stage == ogc::BusStage::Convolver && bus_stage; }
     uint32_t conv_fade_len() const { return (uint32_t)std::max(1.0f, roundf(0.02f * sr)); } // prepare(): CROSSFADE_SECONDS * sr, rounded, >= 1
-    std::shared_ptr<ConvIR> conv_upload(const float* taps, size_t n)
+    std::shared_ptr<ConvIR> conv_upload(const float* taps, size_t n, uint32_t planes = 1) // n taps per plane
     {
         auto ir = std::make_shared<ConvIR>();
-        ir->taps.assign(taps, taps + n);
+        ir->planes = n ? planes : 1u;
+        ir->taps.assign(taps, taps + n * ir->planes);
         if (n) {
-            HIPCK(hipMalloc(&ir->d, n * 4));
+            HIPCK(hipMalloc(&ir->d, ir->taps.size() * 4));
             conv_bufs.push_back(ir->d);
-            bounce.h2d(ir->d, ir->taps.data(), n * 4, stream);
+            bounce.h2d(ir->d, ir->taps.data(), ir->taps.size() * 4, stream);
         }
         return ir;
     }
+    // og_set_bus_ir on an asset response: conformed to the engine's rate and mapped onto the bus's channels on the device
+    std::shared_ptr<ConvIR> conv_build_asset(const std::string& name, const ogc::IrAsset& a);
     void conv_retire(std::shared_ptr<ConvIR>& ir) { ir.reset(); }
     void conv_gc() // free the taps no response in use points at; only with nothing queued and the stream idle
     {

@@ -378,9 +378,9 @@ std::map<std::string, UserFunction>& function_registry()
     static std::map<std::string, UserFunction> R;
     return R;
 }
-std::map<std::string, std::shared_ptr<const std::vector<float>>>& ir_registry()
+std::map<std::string, IrEntry>& ir_registry()
 {
-    static std::map<std::string, std::shared_ptr<const std::vector<float>>> R;
+    static std::map<std::string, IrEntry> R;
     return R;
 }
 const UserFunction* lookup_function(const std::string& path, const std::string& last)
@@ -2874,7 +2874,8 @@ std::string ir_call_path(const std::string& text)
     return t;
 }
 } // namespace
-void register_ir(const std::string& name, const float* taps, size_t n_taps)
+namespace {
+void check_ir_name(const std::string& name)
 {
     size_t b = 0;
     for (;;) { // every path segment an identifier, like a function's name
@@ -2883,11 +2884,36 @@ void register_ir(const std::string& name, const float* taps, size_t n_taps)
         if (c == std::string::npos) break;
         b = c + 2;
     }
+}
+} // namespace
+void register_ir(const std::string& name, const float* taps, size_t n_taps)
+{
+    check_ir_name(name);
     if (n_taps > MAX_IR_TAPS) fail_unsupported("impulse response '" + name + "': " + std::to_string(n_taps) + " taps (at most " + std::to_string(MAX_IR_TAPS) + ")");
-    ir_registry()[name] = std::make_shared<const std::vector<float>>(taps, taps + n_taps);
+    IrEntry e;
+    e.taps = std::make_shared<const std::vector<float>>(taps, taps + n_taps);
+    ir_registry()[name] = e;
+}
+void register_ir_asset(const std::string& name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t rate)
+{
+    check_ir_name(name);
+    // AudioAsset::from_samples' own checks (asset/mod.rs:175-192): a zero rate and an empty asset are refused
+    if (rate == 0) fail("impulse response '" + name + "': the sample rate is 0");
+    if (frames == 0) fail("impulse response '" + name + "': the response is empty");
+    if (!interleaved) fail("impulse response '" + name + "': null data");
+    if (channels < 1 || channels > MAX_IR_ASSET_CHANNELS) fail("impulse response '" + name + "': 1 to " + std::to_string(MAX_IR_ASSET_CHANNELS) + " channels");
+    if (frames > MAX_IR_ASSET_FLOATS / channels) fail("impulse response '" + name + "' has more than 2^28 samples (frames x channels)");
+    auto a = std::make_shared<IrAsset>();
+    a->interleaved.assign(interleaved, interleaved + (size_t)frames * channels);
+    a->frames = (uint32_t)frames;
+    a->channels = channels;
+    a->rate = rate;
+    IrEntry e;
+    e.asset = a;
+    ir_registry()[name] = e;
 }
 bool unregister_ir(const std::string& name) { return ir_registry().erase(name) > 0; }
-std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved)
+IrEntry lookup_ir_entry(const std::string& call_text, std::string* resolved)
 {
     const std::string path = ir_call_path(call_text);
     const size_t c = path.rfind("::");
@@ -2901,8 +2927,9 @@ std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text
             const std::string& k = kv.first;
             if (k.size() > last.size() + 2 && k.compare(k.size() - last.size() - 2, std::string::npos, "::" + last) == 0) return kv.second;
         }
-    return it == R.end() ? nullptr : it->second;
+    return it == R.end() ? IrEntry{} : it->second;
 }
+std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved) { return lookup_ir_entry(call_text, resolved).taps; }
 
 void register_user_node(const UserNodeType& t)
 {
@@ -3431,7 +3458,11 @@ void Lowering::declare_nodes()
                 if (nti->nargs == 1) {
                     const std::string raw = nd.raw_args.empty() ? std::string() : nd.raw_args[0];
                     if (raw.empty()) fail("node '" + nd.name + "': Convolver::with_ir takes the name of a registered impulse response (og_register_ir)");
-                    out.bus_ir = lookup_ir(raw, &out.bus_ir_name);
+                    const IrEntry ire = lookup_ir_entry(raw, &out.bus_ir_name);
+                    if (ire.asset) // (the reference's with_ir is the mono, session-rate constructor; an asset arrives through the `ir` slot)
+                        fail("node '" + nd.name + "': impulse response '" + out.bus_ir_name + "' is an asset response (og_register_ir_asset / og_register_ir_wav): " +
+                             "Convolver::with_ir takes a mono response at the session rate -- build the node with Convolver::new() and publish the asset with og_set_bus_ir");
+                    out.bus_ir = ire.taps;
                     if (!out.bus_ir) fail("unknown impulse response '" + out.bus_ir_name + "' (node '" + nd.name + "'); responses are registered with og_register_ir");
                 }
             } else {

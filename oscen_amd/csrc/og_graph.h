@@ -258,6 +258,25 @@ bool unregister_user_function(const std::string& name);
 void register_ir(const std::string& name, const float* taps, size_t n_taps);
 bool unregister_ir(const std::string& name);
 std::shared_ptr<const std::vector<float>> lookup_ir(const std::string& call_text, std::string* resolved = nullptr);
+// ... and the ASSET form beside it, in the same name space (a name holds one form; registering either replaces what the name
+// held): 1..8 channels of interleaved frames at their own rate -- the reference's `#[input(asset)] ir` slot, an AudioAsset
+// handed to ConvolverConsumer::build.  It is published with og_set_bus_ir, which conforms it to the engine's rate and maps
+// its channels onto the bus's; `Convolver::with_ir` (the reference's mono, session-rate constructor) refuses it.
+struct IrAsset {
+    std::vector<float> interleaved; // [frames][channels]
+    uint32_t frames = 0, channels = 0, rate = 0;
+};
+constexpr uint32_t MAX_IR_ASSET_CHANNELS = 8;             // (MAX_CONV_CHANNELS, convolution/mod.rs:310)
+constexpr uint64_t MAX_IR_ASSET_FLOATS = (uint64_t)1 << 28; // frames x channels, as for samples
+// (throws on a bad name, a zero rate, no frames, null data, a channel count outside 1..8, more than 2^28 samples)
+void register_ir_asset(const std::string& name, const float* interleaved, uint64_t frames, uint32_t channels, uint32_t rate);
+// what a name holds: `taps` (the mono form), `asset`, or neither
+struct IrEntry {
+    std::shared_ptr<const std::vector<float>> taps;
+    std::shared_ptr<const IrAsset> asset;
+    explicit operator bool() const { return taps || asset; }
+};
+IrEntry lookup_ir_entry(const std::string& call_text, std::string* resolved = nullptr);
 constexpr size_t MAX_IR_TAPS = (size_t)1 << 20; // (og_bus_conv.hip.h: OG_CONV_MAX_TAPS)
 constexpr size_t MAX_PLAYERS = 4;                   // SamplePlayer nodes per graph
 

@@ -34,6 +34,12 @@ struct SnapConv {
     uint32_t hist_frames, reserved;
 };
 constexpr uint32_t SNAP_CONV_MAGIC = 0x56434E4Fu; // "ONCV"
+// ... and, ONLY when a live response has one tap plane per channel (an asset response, og_set_bus_ir; a blob without one
+// stays what it was), the section has another magic and `reserved` holds the planes of the two responses (current | outgoing
+// << 16); the taps of a response are then its planes back to back, k taps each
+constexpr uint32_t SNAP_CONVP_MAGIC = 0x50434E4Fu; // "ONCP"
+uint32_t conv_planes(const std::shared_ptr<og_engine::ConvIR>& ir) { return ir ? ir->planes : 1u; }
+bool conv_per_channel(const og_engine* e) { return conv_planes(e->conv.cur) > 1 || conv_planes(e->conv.old) > 1; }
 size_t conv_hist_frames(const og_engine* e)
 {
     const uint32_t k = std::max(e->conv.cur ? e->conv.cur->K() : 0u, e->conv.old ? e->conv.old->K() : 0u);
@@ -42,7 +48,7 @@ size_t conv_hist_frames(const og_engine* e)
 size_t conv_bytes(const og_engine* e)
 {
     if (!e->conv_on()) return 0;
-    return sizeof(SnapConv) + ((size_t)(e->conv.cur ? e->conv.cur->K() : 0u) + (e->conv.old ? e->conv.old->K() : 0u) +
+    return sizeof(SnapConv) + ((e->conv.cur ? e->conv.cur->taps.size() : 0u) + (e->conv.old ? e->conv.old->taps.size() : 0u) +
                                conv_hist_frames(e) * e->cg->voice_channels) * 4;
 }
 
@@ -160,13 +166,16 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
             const auto& cv = e->conv;
             const uint32_t kc = cv.cur ? cv.cur->K() : 0u, ko = cv.old ? cv.old->K() : 0u;
             const size_t hf = conv_hist_frames(e), vc = e->cg->voice_channels;
-            const SnapConv sc{SNAP_CONV_MAGIC, (uint32_t)vc, kc, cv.old ? ko : 0xFFFFFFFFu, cv.cur_from, cv.old_from, cv.fade_start, (uint32_t)hf, 0u};
+            const bool per_channel = conv_per_channel(e);
+            const size_t nc = (size_t)kc * conv_planes(cv.cur), no = (size_t)ko * conv_planes(cv.old);
+            const SnapConv sc{per_channel ? SNAP_CONVP_MAGIC : SNAP_CONV_MAGIC, (uint32_t)vc, kc, cv.old ? ko : 0xFFFFFFFFu, cv.cur_from, cv.old_from, cv.fade_start, (uint32_t)hf,
+                              per_channel ? (conv_planes(cv.cur) | (conv_planes(cv.old) << 16)) : 0u};
             memcpy(p, &sc, sizeof sc);
             p += sizeof sc;
-            if (kc) memcpy(p, cv.cur->taps.data(), (size_t)kc * 4);
-            p += (size_t)kc * 4;
-            if (ko) memcpy(p, cv.old->taps.data(), (size_t)ko * 4);
-            p += (size_t)ko * 4;
+            if (nc) memcpy(p, cv.cur->taps.data(), nc * 4);
+            p += nc * 4;
+            if (no) memcpy(p, cv.old->taps.data(), no * 4);
+            p += no * 4;
             if (hf) e->bounce.d2h(p, e->d_hist + (e->hist_pos - hf) * vc, hf * vc * 4, e->stream); // (hf <= hist_keep <= hist_pos)
             p += hf * vc * 4;
         }
@@ -225,7 +234,8 @@ int og_load_state(og_engine* e, const void* src, size_t len)
                 if (full_len - at < sizeof pc) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
                 memcpy(&pc, (const char*)src + at, sizeof pc);
                 const uint64_t ko = pc.k_old == 0xFFFFFFFFu ? 0u : pc.k_old;
-                const uint64_t n = sizeof pc + ((uint64_t)pc.k_cur + ko + (uint64_t)pc.hist_frames * pc.channels) * 4;
+                const uint64_t pl_cur = pc.magic == SNAP_CONVP_MAGIC ? (pc.reserved & 0xFFFFu) : 1u, pl_old = pc.magic == SNAP_CONVP_MAGIC ? (pc.reserved >> 16) : 1u;
+                const uint64_t n = sizeof pc + ((uint64_t)pc.k_cur * pl_cur + ko * pl_old + (uint64_t)pc.hist_frames * pc.channels) * 4;
                 if (n > full_len - at) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
                 at += (size_t)n;
             }
@@ -285,14 +295,23 @@ int og_load_state(og_engine* e, const void* src, size_t len)
         if (rc != OG_OK) return rc;
     }
     SnapConv sc{};
+    uint32_t pl_cur = 1, pl_old = 1; // tap planes of the two responses
     if (e->conv_on()) {
         bool ok = full_len - len >= sizeof sc;
         if (ok) memcpy(&sc, (const char*)src + len, sizeof sc);
-        ok = ok && sc.magic == SNAP_CONV_MAGIC && sc.channels == e->cg->voice_channels && sc.k_cur <= ogc::MAX_IR_TAPS &&
+        const bool per_channel = ok && sc.magic == SNAP_CONVP_MAGIC;
+        if (per_channel) {
+            pl_cur = sc.reserved & 0xFFFFu;
+            pl_old = sc.reserved >> 16;
+            // a plane per bus channel or one shared plane, and at least one response with planes of its own
+            ok = (pl_cur == 1 || pl_cur == sc.channels) && (pl_old == 1 || pl_old == sc.channels) && (pl_cur > 1 || pl_old > 1) &&
+                 (pl_cur == 1 || sc.k_cur > 0) && (pl_old == 1 || (sc.k_old != 0xFFFFFFFFu && sc.k_old > 0));
+        }
+        ok = ok && (sc.magic == SNAP_CONV_MAGIC || per_channel) && sc.channels == e->cg->voice_channels && sc.k_cur <= ogc::MAX_IR_TAPS &&
              (sc.k_old == 0xFFFFFFFFu || sc.k_old <= ogc::MAX_IR_TAPS);
         const uint64_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old, kmax = std::max<uint64_t>(sc.k_cur, ko);
         ok = ok && sc.hist_frames == (kmax ? kmax - 1 : 0) &&
-             full_len - len == sizeof sc + ((size_t)sc.k_cur + ko + (size_t)sc.hist_frames * sc.channels) * 4;
+             full_len - len == sizeof sc + ((size_t)sc.k_cur * pl_cur + ko * pl_old + (size_t)sc.hist_frames * sc.channels) * 4;
         if (!ok) return set_err(OG_E_INVALID, "state blob: the post-mix Convolver's section is missing or malformed");
     } else if (full_len != len) {
         return set_err(OG_E_INVALID, "state blob does not belong to this graph / voice count (or is from another version)");
@@ -348,8 +367,9 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             const size_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old;
             const float* q = (const float*)((const char*)src + len + sizeof sc);
             if (sc.hist_frames > e->hist_keep) e->conv_alloc(sc.hist_frames);
-            e->conv.cur = e->conv_upload(q, sc.k_cur);
-            e->conv.old = sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + sc.k_cur, ko);
+            const size_t nc = (size_t)sc.k_cur * pl_cur, no = ko * pl_old;
+            e->conv.cur = e->conv_upload(q, sc.k_cur, pl_cur);
+            e->conv.old = sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + nc, ko, pl_old);
             e->conv.cur_from = sc.cur_from;
             e->conv.old_from = sc.old_from;
             e->conv.fade_start = sc.fade_start;
@@ -357,7 +377,7 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             HIPCK(hipMemsetAsync(e->d_hist, 0, e->hist_len * vc * 4, e->stream));
             e->hist_pos = e->hist_keep;
             if (sc.hist_frames)
-                e->bounce.h2d(e->d_hist + (e->hist_pos - sc.hist_frames) * vc, q + sc.k_cur + ko, (size_t)sc.hist_frames * vc * 4, e->stream);
+                e->bounce.h2d(e->d_hist + (e->hist_pos - sc.hist_frames) * vc, q + nc + no, (size_t)sc.hist_frames * vc * 4, e->stream);
             HIPCK(hipStreamSynchronize(e->stream));
             e->conv_gc();
         }

@@ -143,6 +143,18 @@ int og_register_sample_wav(const char* name, const char* path)
     });
 }
 
+int og_register_ir_wav(const char* name, const char* path)
+{
+    return ogabi::guard([&]() -> int {
+    if (!name || !*name || !path) return ogabi::set_error(OG_E_INVALID, "og_register_ir_wav: a response needs a name and a path");
+    ogwav::Decoded d;
+    std::string why;
+    const int rc = ogwav::read(path, d, why);
+    if (rc != OG_OK) return ogabi::set_error(rc, "og_register_ir_wav: '" + std::string(path) + "': " + why);
+    return og_register_ir_asset(name, d.interleaved.data(), d.frames, d.channels, d.sample_rate);
+    });
+}
+
 int og_write_wav(const char* path, const float* interleaved, uint64_t frames, uint32_t channels,
                  uint32_t sample_rate, uint32_t bits_per_sample)
 {
