@@ -1377,16 +1377,10 @@ void emit_tpt(NodeCtx& x)
         // first frame of the block, so it runs in derive() (block start and after per-voice value events)
         x.cg.S().derive << "        og::tpt_params_nomod(" << cutoff.e << ", " << q.e << ", " << tail;
         x.cg.any_derive = true;
-    } else if (nomod && ogabi::experiment_knob("OGC_TPT_FLAT") && atoi(ogabi::experiment_knob("OGC_TPT_FLAT")) != 0) {
-        // experiment: branch-free update (see og::tpt_params_nomod_flat); measured slower on MI355X for
-        // fm_voice (65 536 voices 0.098 ms against 0.087 ms; 262 144 voices 0.293 against 0.234): the
-        // branch is wave-uniformly skipped whenever no lane's envelope moves
-
-        std::string iq;
-        if (block_const(q)) iq = x.hoist("inv_q", "1.0f / og::clampf(" + q.e + ", 0.1f, 10.0f)");
-        else iq = "(1.0f / og::clampf(" + q.e + ", 0.1f, 10.0f))";
-        x.cg.os() << "        og::tpt_params_nomod_flat(" << cutoff.e << ", " << q.e << ", " << iq << ", " << tail;
-    } else if (nomod && x.n.domain != 1 && !(ogabi::experiment_knob("OGC_TPT_LAZY") && atoi(ogabi::experiment_knob("OGC_TPT_LAZY")) == 0)) {
+    } else if (nomod && x.n.domain != 1) {
+        // (the branch-free update, og::tpt_params_nomod_flat, measured slower on MI355X for fm_voice -- 65 536 voices 0.098 ms
+        // against 0.087 ms; 262 144 voices 0.293 against 0.234: the branch is wave-uniformly skipped whenever no lane's
+        // envelope moves)
         // cutoff computed per frame: watch the raw input, run the reference's test only on frames whose input differs from
         // the previous frame's (og::tpt_params_nomod_lazy).  q is watched too when it can change inside a launch: a ramped
         // input (the RAMPS variants of the kernel) or a per-frame value.
@@ -3781,13 +3775,9 @@ void Lowering::prune_dead_nodes()
     // profiles/r03_epiano_lanes.md): 16 lanes x 2 harmonics 0.95e11, 8 x 4 (round 2) 1.15e11, 4 x 8 1.26e11 at two
     // waves per SIMD and 1.28e11 at three -- the per-voice bookkeeping (ramp step, interpolation weights, event and
     // bus plumbing: ~15 of the 38 instructions a lane issues per frame at 8 x 4) is paid once per lane, so fewer lanes
-    // per voice amortise it over more harmonics; 156 VGPRs still leave three waves per SIMD.  OGC_HPL=2|4|8 overrides;
-    // the state layout [voice][32] does not depend on it.
-    int hpl = 8;
-    if (const char* eh = ogabi::experiment_knob("OGC_HPL")) {
-        const int h = atoi(eh);
-        if (h == 2 || h == 4 || h == 8) hpl = h;
-    }
+    // per voice amortise it over more harmonics; 156 VGPRs still leave three waves per SIMD.  The state layout [voice][32]
+    // does not depend on it.
+    const int hpl = 8;
     if (out.lpv > 1) out.lpv = 32 / hpl;
     out.lane_width = out.lpv > 1 ? hpl : 1; // OG_HPL
     for (size_t i = 0; i < g.nodes.size(); ++i)
@@ -3840,15 +3830,13 @@ void Lowering::kahn_order()
 // FMVoice: env3 op3 route env2 op2 | mixer env1 op1 env_filter gain cutoff_mod filter output_gain -- the contiguous
 // two-wave cut now balances (56 | 54 estimated VALU per frame; the Kahn order could only offer 47 | 63), every
 // hand-off value but two stays inside its wave, and the ordinary kernel holds fewer values across nodes.
-// OGC_ALAP=0 keeps the Kahn order (A/B).
 void Lowering::schedule_order()
 {
     bool any_delay_node = false;
     for (int ni : order) any_delay_node = any_delay_node || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
     bool any_rate = false;
     for (int ni : order) any_rate = any_rate || cg.nodes[ni].decl->rate_factor != 1;
-    const bool reorder = !(ogabi::experiment_knob("OGC_ALAP") && atoi(ogabi::experiment_knob("OGC_ALAP")) == 0) && !any_feedback && !cg.dynamic_events && !any_delay_node &&
-                         !any_rate && out.lpv == 1 && order.size() >= 3;
+    const bool reorder = !any_feedback && !cg.dynamic_events && !any_delay_node && !any_rate && out.lpv == 1 && order.size() >= 3;
     if (reorder) {
         std::vector<int> pos(g.nodes.size(), -1);
         for (size_t k = 0; k < order.size(); ++k) pos[order[k]] = (int)k;
@@ -3923,48 +3911,11 @@ void Lowering::plan_pipeline_stages()
 {
     cg.stage_of.assign(g.nodes.size(), 0);
     cg.n_stages = 1;
-    bool stereo_out = false;
-    const char* env_split = ogabi::experiment_knob("OGC_SPLIT");
     bool any_delay = false; // delay lines are staged per chunk by the ordinary kernel only
     for (int ni : order) any_delay = any_delay || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
     for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
-    // a Frame<2> voice output (two bus tiles) is summed by the ordinary kernel only
-    std::function<int(const ExprP&)> width_of = [&](const ExprP& e) -> int {
-        if (!e) return 1;
-        if (e->t == Expr::Ref && !e->port.empty()) {
-            auto nit = cg.node_by_name.find(e->node);
-            if (nit == cg.node_by_name.end()) return 1;
-            const NodeTypeInfo* ti = cg.nodes[nit->second].type;
-            for (size_t o = 0; o < ti->outputs.size() && o < ti->out_channels.size(); ++o)
-                if (e->port == ti->outputs[o]) return ti->out_channels[o];
-            return 1;
-        }
-        if (e->t == Expr::Ref) { // a Frame<N> stream input of the graph
-            auto iit = cg.input_by_name.find(e->node);
-            return iit == cg.input_by_name.end() ? 1 : std::max(1, out.inputs[iit->second].decl.channels);
-        }
-        if (e->t == Expr::Chan || e->t == Expr::Method) return 1;
-        if (e->t == Expr::Call) {
-            if (e->port == "Frame") return (int)e->args.size();
-            const UserFunction* f = lookup_function(e->node, e->port);
-            return f ? f->result_channels : 1;
-        }
-        return std::max(width_of(e->a), width_of(e->b));
-    };
-    for (auto& kv : out_edges)
-        for (auto& src : kv.second) stereo_out = stereo_out || width_of(src.src) >= 2;
-    for (size_t oi = 0; oi < g.outputs.size(); ++oi) // (a declared `output out: stream: Frame<2>`)
-        stereo_out = stereo_out || (g.outputs[oi].kind == Kind::Stream && g.outputs[oi].channels >= 2);
-    // (several stream outputs = several bus channels: summed by the ordinary kernel only, like a Frame<2> output)
-    {
-        int n_stream_outs = 0;
-        for (size_t oi = 0; oi < g.outputs.size(); ++oi)
-            if (g.outputs[oi].kind == Kind::Stream && out_edges.count((int)oi) && (int)oi != bus_src_output) ++n_stream_outs;
-        if (n_stream_outs > 1 && out.bus_stage != BusStage::Tremolo) stereo_out = true;
-    }
-    bool want = !(env_split && atoi(env_split) == 0) && cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
+    bool want = cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
                 !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
-    (void)stereo_out;
     // estimated per-tick VALU cost of every node, in emission order
     int total = 0;
     std::vector<int> w;
@@ -4121,32 +4072,7 @@ void Lowering::plan_pipeline_stages()
             cg.stage_of[order[k]] = st;
         }
         cg.groups2 = grouping(2);
-        if (const char* ec = ogabi::experiment_knob("OGC_CUT2")) { // experiment knob: first wave = the first k stages
-            const int ku = std::max(1, std::min(cg.n_stages - 1, atoi(ec)));
-            cg.groups2 = {{}, {}};
-            for (int k = 0; k < cg.n_stages; ++k) cg.groups2[k < ku ? 0 : 1].push_back(k);
-        }
-        const char* ep = ogabi::experiment_knob("OGC_PARTS");
-        if (total >= 48 && unit_w.size() >= 4 && !(ep && atoi(ep) < 4)) cg.groups4 = grouping(ogabi::experiment_knob("OGC_K3") ? 3 : 4);
-        if (const char* ec = ogabi::experiment_knob("OGC_CUTS")) { // experiment knob: "a,b[,c]" = one-past-last stage of every wave but the last (3 or 4 waves)
-            std::vector<int> ends;
-            for (const char* q = ec; *q;) {
-                ends.push_back(atoi(q));
-                while (*q && *q != ',') ++q;
-                if (*q == ',') ++q;
-            }
-            ends.push_back(cg.n_stages);
-            std::vector<std::vector<int>> gr;
-            int lo = 0;
-            bool ok = ends.size() >= 3 && ends.size() <= 6;
-            for (int e : ends) {
-                ok = ok && e > lo && e <= cg.n_stages;
-                gr.emplace_back();
-                for (int k = lo; k < e && ok; ++k) gr.back().push_back(k);
-                lo = e;
-            }
-            if (ok) cg.groups4 = gr;
-        }
+        if (total >= 48 && unit_w.size() >= 4) cg.groups4 = grouping(4);
     }
     cg.split = cg.n_stages > 1;
 }
@@ -4370,7 +4296,6 @@ void Lowering::choose_unroll()
         else if (cg.N > 1) unroll = 16;
         else unroll = (has_env && graph_weight >= 70) ? 4 : 8; // (fm_voice: sixteen is worth +0.7 % over four and brings spills into the tapped variants' chunk bodies)
     }
-    if (const char* u = ogabi::experiment_knob("OGC_UNROLL")) unroll = std::max(1, std::min(16, atoi(u)));
 }
 
 // ---- the body writer: the kernel text of a lowered graph, assembled from the per-stage sections the nodes wrote --------
@@ -4382,12 +4307,12 @@ struct BodyWriter {
     const std::string& bus_expr;
     const int unroll;
     std::vector<int> all_stages;
-    const bool chunk_chk; // the chunk variants without stage-end checks exist (OGC_CHUNK_CHK=0 / node-to-node events: off)
+    const bool chunk_chk; // the chunk variants without stage-end checks exist (node-to-node events: off)
     std::ostringstream body;
 
     explicit BodyWriter(const Lowering& lw)
         : cg(lw.cg), g(lw.g), out(lw.out), order(lw.order), bus_expr(lw.bus_expr), unroll(lw.unroll),
-          chunk_chk(!(ogabi::experiment_knob("OGC_CHUNK_CHK") && atoi(ogabi::experiment_knob("OGC_CHUNK_CHK")) == 0) && !cg.dynamic_events)
+          chunk_chk(!cg.dynamic_events)
     {
         for (int k = 0; k < cg.n_stages; ++k) all_stages.push_back(k);
     }
@@ -4396,6 +4321,8 @@ struct BodyWriter {
     std::string vin_store();
     std::string cat(const std::vector<int>& st, std::ostringstream Codegen::Sect::*m);
     static int group_of(const std::vector<std::vector<int>>& groups, int stage);
+    static bool reads_across(const std::vector<std::vector<int>>& groups, const Codegen::XVal& xv, int gi);
+    static int ring_depth(const std::vector<std::vector<int>>& groups, const Codegen::XVal& xv);
     std::string group_tick(const std::vector<std::vector<int>>& groups, int gi);
     std::string min_cnt(const std::vector<int>& st);
     std::string rs_sum(const std::vector<int>& st);
@@ -4479,6 +4406,22 @@ int BodyWriter::group_of(const std::vector<std::vector<int>>& groups, int stage)
         return -1;
 }
 
+// group `gi` reads the value, and another group makes it: it arrives through the value's LDS ring
+bool BodyWriter::reads_across(const std::vector<std::vector<int>>& groups, const Codegen::XVal& xv, int gi)
+{
+        bool used_here = false;
+        for (int u : xv.users) used_here = used_here || group_of(groups, u) == gi;
+        return used_here && group_of(groups, xv.from) != gi;
+}
+
+// chunks in the LDS ring of a value: from its producer's group to its farthest reader's (1: it stays in its wave)
+int BodyWriter::ring_depth(const std::vector<std::vector<int>>& groups, const Codegen::XVal& xv)
+{
+        int far = group_of(groups, xv.from);
+        for (int u : xv.users) far = std::max(far, group_of(groups, u));
+        return far - group_of(groups, xv.from) + 1;
+}
+
 // per-frame code of one group: stage code in order; a value read by a later stage is aliased right
 // after its producer (same wave) or travels through its LDS channel (other wave)
 std::string BodyWriter::group_tick(const std::vector<std::vector<int>>& groups, int gi)
@@ -4487,9 +4430,7 @@ std::string BodyWriter::group_tick(const std::vector<std::vector<int>>& groups, 
         const std::vector<int>& st = groups[gi];
         for (size_t k = 0; k < cg.xvals.size(); ++k) {
             const auto& xv = cg.xvals[k];
-            bool used_here = false;
-            for (int u : xv.users) used_here = used_here || group_of(groups, u) == gi;
-            if (used_here && group_of(groups, xv.from) != gi) // (quiet chunks: read at the top of the chunk into xp<k>[])
+            if (reads_across(groups, xv, gi)) // (quiet chunks: read at the top of the chunk into xp<k>[])
                 t << "        const float " << xv.alias << " = [&]() __attribute__((always_inline)) { if constexpr (decltype(chk)::pre) return xp"
                   << k << "[j]; else return chan" << k << "[ch % XD" << k << "][j][c.lane]; }();\n";
         }
@@ -4551,7 +4492,6 @@ void BodyWriter::write_ordinary_kernel()
          << "    og::VoiceCtx c;\n"
          << "    og::voice_begin<TAPS, LPV>(A, c);\n"
          << "    og::bus_init(c, bus);\n"
-         << (ogabi::experiment_knob("OGC_PRIO_PARITY") ? "    if ((blockIdx.x >> 3) & 1u) __builtin_amdgcn_s_setprio(1); // experiment\n" : "")
          << cg.common_decl.str() << cat(all_stages, &Codegen::Sect::decl) << "    if (c.valid) {\n"
          << cg.common_load.str() << cat(all_stages, &Codegen::Sect::load) << "    }\n";
     body << "    auto derive = [&]() __attribute__((always_inline)) {\n" << cat(all_stages, &Codegen::Sect::derive) << "    };\n";
@@ -4578,14 +4518,14 @@ void BodyWriter::write_ordinary_kernel()
         std::string steady;
         for (int k : all_stages)
             for (const auto& fc : cg.sec[k].fast_conds) steady += (steady.empty() ? "" : " && ") + fc;
-        // Sticky chunks in the ordinary kernel (OGC_STICKY1=0 turns them off): as in the pipelined kernels (emit_pipeline below), a wave stays in the quiet variant it is in while that
-        // variant's conditions hold on the next chunk, instead of going back through the chunk loop's head, where the
-        // compiler reconciles the register assignments of the four chunk bodies (fm_voice: 57 v_mov per 16-frame chunk).
-        const bool sticky1 = !(ogabi::experiment_knob("OGC_STICKY1") && atoi(ogabi::experiment_knob("OGC_STICKY1")) == 0); // round 5: on (+4.5 % at 262 144 voices, +6 % at 1 M, +3.4 % saturator; profiles/r05a_session1.md)
+        // Sticky chunks in the ordinary kernel: as in the pipelined kernels (PipelineWave below), a wave stays in the quiet
+        // variant it is in while that variant's conditions hold on the next chunk, instead of going back through the chunk
+        // loop's head, where the compiler reconciles the register assignments of the four chunk bodies (fm_voice: 57 v_mov per
+        // 16-frame chunk).  Round 5: +4.5 % at 262 144 voices, +6 % at 1 M, +3.4 % saturator (profiles/r05a_session1.md).
         std::string stay_path1;
         auto variants = [&](const std::string& tail, const std::string& ind0) {
             auto quiet = [&](const std::string& flag, const std::string& ind1, const std::string& stay = std::string()) {
-                const bool loop = sticky1 && !stay.empty();
+                const bool loop = !stay.empty();
                 const std::string ind = loop ? ind1 + "    " : ind1;
                 if (loop) body << ind1 << "for (;;) { // sticky: this variant again while its conditions hold\n";
                 if (flag != "false, false") body << fc_sync(all_stages, ind);
@@ -4660,14 +4600,11 @@ struct PipelineWave {
     std::vector<std::string> envs; // "<E>" of this wave's outer-rate envelopes
     std::set<int> rows;            // ramp-table rows its tick reads
     std::string tick_text, steady, mc;
-    bool sticky = true;
     std::string stay_path; // conditions of the enclosing branches, on the next chunk
     std::set<int> producers, consumers;
     std::string wait_all, taken, sync_line;
     bool tab_ok = false;
     bool stage_bodies = false; // this wave has the hold and the pure-release body (the deeper zero variant, four waves, envelopes)
-    const char* force = nullptr;
-    int rel_prio = -1;
 
     PipelineWave(BodyWriter& w, const std::vector<std::vector<int>>& gr, int group)
         : bw(w), body(w.body), cg(w.cg), out(w.out), groups(gr), K((int)gr.size()), gi(group), st(gr[(size_t)group]), last(group == K - 1)
@@ -4681,6 +4618,7 @@ struct PipelineWave {
     std::string call_as(const std::string& chk) const;
     std::string bus_tail(const std::string& ind, const std::string& n_expr) const;
     std::string row_fetch(const std::string& ind) const;
+    void prefetch(const std::string& ind);
     void quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay = std::string(), int env_mode = 0);
     void checked(const std::string& ind);
     void variants(bool st_flag, const std::string& ind0);
@@ -4691,37 +4629,26 @@ struct PipelineWave {
 void BodyWriter::pipeline_lds(const std::vector<std::vector<int>>& groups)
 {
     const int K = (int)groups.size();
-    // frames per hand-off: 8.  16 (OGC_XCH16, two-wave pipeline only) measured +2% on a 94-block run at
+    // frames per hand-off: 8.  16 in the two-wave pipeline measured +2% on a 94-block run at
     // 65 536 voices but -1.5% on the 188-block default run, and its doubled LDS rings leave room for only
     // four workgroups per CU: 98 304 voices (six per CU) ran 29% slower.  4 is 11% slower.
+    // (With the sticky chunk loops a hand-off costs ~9 VALU + ~17 SALU and a barrier instead of ~45 + ~40, so the trade
+    // between hand-off overhead (longer chunks) and lock-step wait / LDS footprint (shorter ones) has moved since those
+    // measurements.  OG_BUS_CHUNK (16) must stay a multiple.)
     size_t slots = 0;
     for (const auto& xv : cg.xvals) {
-        int far = group_of(groups, xv.from);
-        for (int u : xv.users) far = std::max(far, group_of(groups, u));
-        const int depth = far - group_of(groups, xv.from) + 1;
+        const int depth = ring_depth(groups, xv);
         if (depth > 1) slots += (size_t)depth;
-    }
-    const bool wide = K == 2 && slots * 16 * 64 * 4 <= 36 * 1024 && ogabi::experiment_knob("OGC_XCH16");
-    int xch = wide ? 16 : 8;
-    // OGC_XCH=4|16: experiment for the next round -- with the sticky chunk loops a hand-off costs ~9 VALU + ~17 SALU
-    // and a barrier instead of ~45 + ~40, so the trade between hand-off overhead (longer chunks) and lock-step wait /
-    // LDS footprint (shorter ones) has moved since the measurements above.  OG_BUS_CHUNK (16) must stay a multiple.
-    if (const char* ex = ogabi::experiment_knob("OGC_XCH")) {
-        const int want = atoi(ex);
-        if ((want == 4 || want == 8 || want == 16) && slots * (size_t)want * 64 * 4 <= 60 * 1024) xch = want;
     }
     // Round 5: the four-wave kernel waits more than it issues (54 % of its wave cycles), and 16-frame hand-offs -- half
     // the barriers -- measured +2.4 % at the driver's command and +3.3 % on 94-block regions at 65 536 voices; but
     // their LDS rings (fm_voice: 36.9 KB per workgroup) fit only four workgroups per CU, so a bank of five or six per
     // CU would run in two rounds.  Both exist: XCH_T = 16 instantiates the wide form (og_k4w_*), which the engine
     // launches when every workgroup of the bank is resident at once (og_engine.cpp, depth model).
-    body << "    constexpr uint32_t XCH = XCH_T ? XCH_T : " << xch << "u; // frames per hand-off between the waves\n";
-    if (K == 4 && xch == 8 && slots * 16 * 64 * 4 + 4160 * (size_t)std::max(1u, out.voice_channels) <= 40 * 1024) out.wide4 = true;
+    body << "    constexpr uint32_t XCH = XCH_T ? XCH_T : 8u; // frames per hand-off between the waves\n";
+    if (K == 4 && slots * 16 * 64 * 4 + 4160 * (size_t)std::max(1u, out.voice_channels) <= 40 * 1024) out.wide4 = true;
     for (size_t k = 0; k < cg.xvals.size(); ++k) {
-        const auto& xv = cg.xvals[k];
-        int far = group_of(groups, xv.from);
-        for (int u : xv.users) far = std::max(far, group_of(groups, u));
-        const int depth = far - group_of(groups, xv.from) + 1;
+        const int depth = ring_depth(groups, cg.xvals[k]);
         body << "    constexpr uint32_t XD" << k << " = " << (depth > 1 ? "FD_T ? FD_T : " : "") << depth << ";\n";
         if (depth > 1) body << "    __shared__ float chan" << k << "[XD" << k << "][XCH][OG_WAVE];\n";
     }
@@ -4754,10 +4681,7 @@ void BodyWriter::write_pipeline_kernel(const std::vector<std::vector<int>>& grou
          << "__device__ __forceinline__ void voice_block_p" << tag << "(const OgBlockArgs& A)\n{\n"
          << "    __shared__ og::" << (out.voice_channels > 1 ? "BusLdsN<" + std::to_string(out.voice_channels) + ">" : std::string("BusLds")) << " bus;\n";
     pipeline_lds(groups);
-    const char* rot_expr[5] = {"0u", "blockIdx.x", "(blockIdx.x >> 3)", "(blockIdx.x >> 5)", "(blockIdx.x >> 8)"};
-    int rot = 1;
-    if (const char* er = ogabi::experiment_knob("OGC_ROT")) rot = std::max(0, std::min(4, atoi(er)));
-    body << "    const uint32_t stage = (threadIdx.x / OG_WAVE + " << rot_expr[rot] << ") % " << K << "u;\n"
+    body << "    const uint32_t stage = (threadIdx.x / OG_WAVE + blockIdx.x) % " << K << "u;\n"
          << "    og::VoiceCtx c;\n"
          << "    og::voice_begin_split<TAPS>(A, c);\n"
          << cg.common_decl.str() << "    if (c.valid) {\n" << cg.common_load.str() << "    }\n"
@@ -4782,7 +4706,7 @@ void PipelineWave::prologue()
         // the pipeline (the light producer: envelopes, first operator) runs at priority 1: it never becomes
         // the straggler its consumers wait for at the hand-off barrier.  Measured, fm_voice: two waves at
         // 65 536 voices 0.0741 -> 0.0660 ms; four waves at 32 768 voices 0.0500 -> 0.0484 ms; raising the
-        // other waves as well (2,1 / 3,2,1,0) is no better.  OGC_PRIO="p0,p1[,p2,p3]" overrides.
+        // other waves as well (2,1 / 3,2,1,0) is no better.
         // Round 4, four waves (depth-first order): the LAST wave (filter, bus) lowest, the first highest, the middle
         // ones between -- 2,1,1,0.  Interleaved A/B at the driver's command, 65 536 voices: 1,0,0,0 3.08e11; 0,0,0,0
         // 3.00e11; 0,0,1,0 3.20e11; 1,1,1,0 3.16e11; 2,1,1,0 3.26e11; 3,2,1,0 3.27e11; 3,2,2,0 3.28e11; 2,1,2,0 3.28e11;
@@ -4794,11 +4718,6 @@ void PipelineWave::prologue()
             pr.front() = 2;
             pr.back() = 0;
         }
-        if (const char* ep = ogabi::experiment_knob("OGC_PRIO")) {
-            pr.clear();
-            for (const char* q = ep; *q; ++q)
-                if (isdigit((unsigned char)*q)) pr.push_back(*q - '0');
-        }
         base_prio = gi < (int)pr.size() ? pr[gi] : 0;
         // Round 6, flag hand-off (FD_T != 0): the order turns round -- 0,1,2,3, downstream first.  Without the barrier a
         // consumer that has its inputs runs them down at once and the producers fill in behind it; the rings stay near
@@ -4807,7 +4726,7 @@ void PipelineWave::prologue()
         // 5.56e11; flags 0,0,0,0 5.40e11; flags 0,1,1,2 5.65e11; 0,0,1,2 5.74e11; 0,1,2,2 5.57e11; 1,1,2,3 5.38e11;
         // 0,0,2,3 5.32e11; flags 0,1,2,3 5.93e11 -- and the barrier with 0,1,2,3 4.89e11: the order only works without
         // the lock step.  Moving-cutoff variant 3.95e11 -> 4.37e11; 188-block regions 6.42e11 -> 6.2e11 (-3 %).
-        const int flag_prio = ogabi::experiment_knob("OGC_PRIO") ? base_prio : std::min(gi, 3);
+        const int flag_prio = std::min(gi, 3);
         body << "    constexpr int BASE_PRIO = FD_T != 0 ? " << flag_prio << " : " << base_prio << ";\n"
              << "    og::set_prio<BASE_PRIO>();\n";
     }
@@ -4816,17 +4735,12 @@ void PipelineWave::prologue()
     body << bw.cat(st, &Codegen::Sect::pre) << "    derive();\n";
     // hand-off values this wave reads: fetched for the whole chunk before its first tick, so that the LDS
     // latency is paid once per chunk and not in front of every frame's first dependent instruction
-    for (size_t k = 0; k < cg.xvals.size(); ++k) {
-        const auto& xv = cg.xvals[k];
-        bool used_here = false;
-        for (int u : xv.users) used_here = used_here || bw.group_of(groups, u) == gi;
-        if (used_here && bw.group_of(groups, xv.from) != gi) reads.push_back(k);
-    }
+    for (size_t k = 0; k < cg.xvals.size(); ++k)
+        if (bw.reads_across(groups, cg.xvals[k], gi)) reads.push_back(k);
     for (size_t k : reads) body << "    float xp" << k << "[XCH];\n";
     // Release reciprocals from a table (four-wave shapes; the sticky release loop below, wide form only, og::rcp_fetch):
     // one 16-byte load per envelope and four frames instead of v_rcp_f32 + a subtraction per envelope and frame.
-    // OGC_RCP_TAB=0 keeps v_rcp_f32 in that loop (A/B).
-    if (K == 4 && !(ogabi::experiment_knob("OGC_RCP_TAB") && atoi(ogabi::experiment_knob("OGC_RCP_TAB")) == 0))
+    if (K == 4)
         for (int k : st)
             for (const auto& cexp : cg.sec[k].env_cnts) envs.push_back(cexp.substr(0, cexp.size() - 4)); // "<E>.cnt"
     for (const auto& E : envs) body << "    float " << E << "_rcp[XCH];\n";
@@ -4893,8 +4807,7 @@ void PipelineWave::handoff_setup()
     // Static count, fm_voice four-wave kernel, release-free quiet chunk of waves 0-2: 231 + 230 + 222 -> ~201 + 187 + 194
     // VALU per 8 frames; rocprofv3 SQ_INSTS_VALU per 64-voice frame at the driver's command 120.7 -> 107.4.  Interleaved A/B on one MI355X, 65 536 voices: 94-block
     // runs 3.73e11 -> 4.01e11, the driver's command 3.29e11 -> 3.54e11, 131 072 voices 3.90e11 -> 4.20e11 (+7.5 % each);
-    // parity subset of the GPU suite green with the variant before it became the default.  OGC_STICKY=0 turns it off.
-    sticky = !(ogabi::experiment_knob("OGC_STICKY") && atoi(ogabi::experiment_knob("OGC_STICKY")) == 0) && !ogabi::experiment_knob("OGC_FORCE_PATH");
+    // parity subset of the GPU suite green with the variant before it became the default.
     // hand-off partners of this wave: the stages whose values it reads (producers) and the stages that read its values
     for (const auto& xv : cg.xvals) {
         const int from = bw.group_of(groups, xv.from);
@@ -4953,6 +4866,17 @@ std::string PipelineWave::row_fetch(const std::string& ind) const
     return o.str();
 }
 
+// the chunk's table rows and hand-off values into registers, at the top of an unrolled body; the ring slots go back at once
+void PipelineWave::prefetch(const std::string& ind)
+{
+    if (reads.empty() && rows.empty()) return;
+    body << row_fetch(ind);
+    body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
+    for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
+    body << ind << "}\n";
+    if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
+}
+
 // The quiet release loop of the four-wave form takes its reciprocals from the table in the wide instantiation
 // (FD_T != 0; the 8-frame one keeps v_rcp_f32): one 16-byte load per envelope and four frames.  A wide launch whose
 // releases the table does not cover (rcp_len = 0) sends chunks with a releasing lane to the checked body instead
@@ -4962,7 +4886,7 @@ std::string PipelineWave::row_fetch(const std::string& ind) const
 void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_flag, const std::string& ind0, const std::string& stay, int env_mode)
 {
     const bool pre = !reads.empty() || !rows.empty();
-    const bool loop = sticky && !stay.empty();
+    const bool loop = !stay.empty();
     const std::string ind = loop ? ind0 + "    " : ind0;
     const bool tab = tab_ok && loop && !envs.empty() && std::string(chk_flag) == "false" && std::string(rel_flag) == "true";
     if (tab) {
@@ -4977,13 +4901,7 @@ void PipelineWave::quiet(const char* chk_flag, const char* rel_flag, bool st_fla
         if (tab) body << ind << "if constexpr (FD_T == 0) {\n" << bw.fc_sync(st, ind + "    ") << ind << "}\n";
         else body << bw.fc_sync(st, ind);
     }
-    if (pre) {
-        body << row_fetch(ind);
-        body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
-        for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
-        body << ind << "}\n";
-        if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
-    }
+    prefetch(ind);
     const std::string flag = std::string(chk_flag) + ", " + rel_flag + ", " + (pre ? "true" : "false") + ", " +
                              (st_flag ? "true" : "false") + (tab ? ", FD_T != 0" : "");
     const std::string stage_flag = std::string("og::StageC<") + (env_mode == 1 ? "og::ENV_HOLD" : "og::ENV_RELEASE") + ", " + (pre ? "true" : "false") + ", " +
@@ -5022,13 +4940,7 @@ void PipelineWave::checked(const std::string& ind)
 {
     const bool pre = !reads.empty() || !rows.empty();
     body << bw.fc_sync(st, ind);
-    if (pre) {
-        body << row_fetch(ind);
-        body << ind << "#pragma unroll\n" << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n";
-        for (size_t k : reads) body << ind << "    xp" << k << "[j] = chan" << k << "[ch % XD" << k << "][j][c.lane];\n";
-        body << ind << "}\n";
-        if (!reads.empty() && !taken.empty()) body << ind << taken << "\n";
-    }
+    prefetch(ind);
     const std::string flag = std::string("true, true, ") + (pre ? "true" : "false") + ", false";
     body << ind << "#pragma unroll\n"
          << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
@@ -5038,24 +4950,8 @@ void PipelineWave::checked(const std::string& ind)
          << ind << "}\n";
 }
 
-void PipelineWave::variants(bool st_flag, const std::string& ind0)
-{
-    if (force && force[0] == 'c') {
-        quiet("true", "true", st_flag, ind0);
-    } else if (mc.empty()) {
-        quiet("true", "true", st_flag, ind0, "1");
-    } else {
-        const std::string no_end = "__all((int)(" + mc + " > (uint32_t)XCH))", no_rel = "__all((int)(" + bw.rs_sum(st) + " == 0.0f))";
-        body << ind0 << "if (" << no_end << ") { // no envelope stage ends in this chunk\n"
-             << ind0 << "    if (" << no_rel << ") { // ... and no lane is in Release\n";
-        quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "        ", no_end + " && " + no_rel);
-        body << ind0 << "    } else {\n";
-        quiet("false", "true", st_flag, ind0 + "        ", no_end + " && !" + no_rel);
-        body << ind0 << "    }\n" << ind0 << "} else {\n";
-        quiet("true", "true", st_flag, ind0 + "    ");
-        body << ind0 << "}\n";
-    }
-}
+// a wave without envelope countdowns: one straight-line variant
+void PipelineWave::variants(bool st_flag, const std::string& ind0) { quiet("true", "true", st_flag, ind0, "1"); }
 
 // the two straight-line variants only (the caller has established that no countdown ends in the chunk)
 void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
@@ -5070,7 +4966,7 @@ void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
         holds += (holds.empty() ? "" : " && ") + ("og::adsr_holds(" + E + ")");
         releases += (releases.empty() ? "" : " && ") + ("og::adsr_releases(" + E + ")");
     }
-    const bool bodies = stage_bodies && tab_ok && sticky;
+    const bool bodies = stage_bodies && tab_ok;
     body << ind0 << "if (" << no_rel << ") { // no lane is in Release\n";
     if (bodies) {
         body << ind0 << "    if (og::stage_spec_on(A) && __all((int)(" << holds << "))) { // ... and every envelope holds its level\n";
@@ -5079,12 +4975,11 @@ void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
         quiet("false", "false", st_flag, ind0 + "        ", no_rel);
         body << ind0 << "    }\n";
     } else {
-        quiet("false", force && force[0] == 'b' ? "true" : "false", st_flag, ind0 + "    ", no_rel);
+        quiet("false", "false", st_flag, ind0 + "    ", no_rel);
     }
     body << ind0 << "} else {\n";
-    // OGC_RELPRIO=n (experiment for grouped banks, og_group_voices: the waves that release are then few and
-    // whole, and their workgroups are the ones a launch waits for; measured WITHOUT grouping in round 4: loses)
-    if (rel_prio >= 0) body << ind0 << "    __builtin_amdgcn_s_setprio(" << rel_prio << ");\n";
+    // (a raised priority for the release variants -- the waves that release are then few and whole in grouped banks,
+    //  og_group_voices, and their workgroups are the ones a launch waits for -- measured WITHOUT grouping in round 4: loses)
     if (bodies) {
         body << ind0 << "    if (og::stage_spec_on(A) && __all((int)(!c.valid || (" << releases << ")))) { // every envelope of every voice releases\n";
         quiet("false", "true", st_flag, ind0 + "        ", "!" + no_rel, 2);
@@ -5094,7 +4989,6 @@ void PipelineWave::fast_variants(bool st_flag, const std::string& ind0)
     } else {
         quiet("false", "true", st_flag, ind0 + "    ", "!" + no_rel);
     }
-    if (rel_prio >= 0) body << ind0 << "    og::set_prio<BASE_PRIO>();\n";
     body << ind0 << "}\n";
 }
 
@@ -5116,12 +5010,10 @@ void PipelineWave::chunk_loop()
     // event falls by a third, nearly all of it from (1)) -- but (2) inlines the handlers into every frame of the
     // checked body (two-wave kernel 26.8 -> 35.9 KB) and the QUIET path pays for it: idle bank 0.0514 -> 0.0528,
     // sustaining 0.0536 -> 0.0553.  At the benchmark's event density the two cancel (2.73e11 either way), so
-    // (1) was on and (2) off through round 3: OGC_EVSKIP=0 turns (1) off.
-    const bool ev_skip = !(ogabi::experiment_knob("OGC_EVSKIP") && atoi(ogabi::experiment_knob("OGC_EVSKIP")) == 0);
+    // (1) was on and (2) off through round 3.
     // (round 4: (2) is ON -- with the event records prefetched into registers (og::VoiceCtx::nx_*) the handlers inlined
     //  into the checked body no longer carry loads and waits; four-wave kernel at 65 536 voices, interleaved A/B:
-    //  3.07e11 either way at the driver's command, 3.57e11 against 3.44e11 on the 188-block run; OGC_EVUNROLL=0 turns it off)
-    const bool ev_unroll = !(ogabi::experiment_knob("OGC_EVUNROLL") && atoi(ogabi::experiment_knob("OGC_EVUNROLL")) == 0);
+    //  3.07e11 either way at the driver's command, 3.57e11 against 3.44e11 on the 188-block run)
     std::string relevant; // condition on `tgt`: this wave has a handler for the event
     {
         const std::string code = bw.cat(st, &Codegen::Sect::derive) + bw.group_tick(groups, gi) + bw.cat(st, &Codegen::Sect::decl);
@@ -5144,17 +5036,14 @@ void PipelineWave::chunk_loop()
         for (int h : handled) relevant += (relevant.empty() ? "" : " || ") + ("tgt == " + std::to_string(h) + "u");
         if (relevant.empty()) relevant = "false";
     }
-    force = ogabi::experiment_knob("OGC_FORCE_PATH"); // experiment knob: b | c | ev -- quiet chunks take the release-arithmetic / stage-end-check / event path (results stay valid)
-    rel_prio = ogabi::experiment_knob("OGC_RELPRIO") ? atoi(ogabi::experiment_knob("OGC_RELPRIO")) : -1;
     if (last) body << "    og::bus_init(c, bus); // (this wave owns the tile)\n";
     body << "    for (uint32_t t = 0; t < n_chunks + (FD_T ? 0u : " << (K - 1) << "u); ++t) {\n"
-         << "        " << (sticky ? "" : "const ") << "uint32_t ch = t - (FD_T ? 0u : " << gi << "u);\n"
+         << "        uint32_t ch = t - (FD_T ? 0u : " << gi << "u);\n"
          << "        if (ch < n_chunks) {\n";
     if (!wait_all.empty()) body << "        " << wait_all << "\n";
-    body
-         << "        " << (sticky ? "" : "const ") << "uint32_t base = ch * XCH;\n"
+    body << "        uint32_t base = ch * XCH;\n"
          << "        const uint32_t n = min((uint32_t)XCH, A.frames - base);\n";
-    if (ev_skip && relevant != "true")
+    if (relevant != "true")
         body << "        if (!__all((int)(c.next_ev >= base + XCH))) { // consume the events this wave has no handler for\n"
              << "            while (c.next_ev < base + XCH) {\n"
              << "                const uint32_t tgt = c.nx_target;\n"
@@ -5169,16 +5058,15 @@ void PipelineWave::chunk_loop()
     // third of it; neutral at 32 768 and 262 144 voices; raising the release-arithmetic variant as well loses
     // the gain.  (The two-wave kernel carries it too although it does nothing for it -- forced with
     // OSCEN_GPU_SPLIT=2 at 65 536 voices: 3.16e11 with, 3.19e11 without; the engine does not pick that kernel at
-    // any bank size of the bench.)  OGC_SLOWPRIO=-1 turns it off.
-    const int slow_prio = ogabi::experiment_knob("OGC_SLOWPRIO") ? atoi(ogabi::experiment_knob("OGC_SLOWPRIO")) : 3;
-    const bool one_checked = ev_unroll && !mc.empty() && !force; // events and stage ends share ONE unrolled, checked body
+    // any bank size of the bench.)
+    const bool one_checked = !mc.empty(); // events and stage ends share ONE unrolled, checked body
     tab_ok = one_checked && !envs.empty();
     const std::string rel_ok = tab_ok ? " && (FD_T == 0 || A.rcp_len != 0u || __all((int)(" + bw.rs_sum(st) + " == 0.0f)))" : std::string();
     if (one_checked)
         body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH)) && __all((int)(" << mc
              << " > (uint32_t)XCH))" << rel_ok << ") { // nothing happens in this chunk: no event, no envelope stage end\n";
     else
-        body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH))" << (force && force[0] == 'e' ? " && A.frames == 0u" : "") << ") {\n";
+        body << "        if (n == XCH && __all((int)(c.next_ev >= base + XCH))) {\n";
     auto pick = [&](bool st_flag, const std::string& ind) {
         if (one_checked) fast_variants(st_flag, ind);
         else variants(st_flag, ind);
@@ -5199,19 +5087,11 @@ void PipelineWave::chunk_loop()
         pick(false, "                ");
         body << "            }\n";
     }
-    if (one_checked && ogabi::experiment_knob("OGC_STAGEEND_BODY") && atoi(ogabi::experiment_knob("OGC_STAGEEND_BODY")) != 0) {
-        // experiment (round 6): a chunk with a stage end but NO event takes a body with the stage-end checks and without
-        // the per-frame event tests and the inlined handlers
-        body << "        } else if (n == XCH && __all((int)(c.next_ev >= base + XCH))) { // a stage end, no event\n";
-        if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << ");\n";
-        quiet("true", "true", false, "            ");
-        if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
-    }
     if (one_checked) {
-        body << "        } else if (n == XCH) { // an event or a stage end in this chunk: the checked, unrolled body\n";
-        if (slow_prio >= 0) body << "            __builtin_amdgcn_s_setprio(" << slow_prio << "); // the wave on the slow path is the straggler\n";
+        body << "        } else if (n == XCH) { // an event or a stage end in this chunk: the checked, unrolled body\n"
+             << "            __builtin_amdgcn_s_setprio(3); // the wave on the slow path is the straggler\n";
         checked("            ");
-        if (slow_prio >= 0) body << "            og::set_prio<BASE_PRIO>();\n";
+        body << "            og::set_prio<BASE_PRIO>();\n";
     }
     body << "        } else {\n"
          << bw.fc_sync(st, "            ")
@@ -5547,13 +5427,8 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     CompiledGraph& out = *gen.out;
     const Codegen& cg = gen.cg;
     // the wide four-wave form: 16-frame chunks, flag hand-off over rings of two chunks (round 6; round 5: one barrier per chunk).
-    // OGC_FLAGS="xch,depth" (experiment): `xch` frames per chunk, rings of `depth` chunks, depth 0 = the barrier
-    std::string wide_args = "16, 2";
-    if (const char* ef = ogabi::experiment_knob("OGC_FLAGS")) {
-        int xch = 0, fd = 0;
-        if (sscanf(ef, "%d,%d", &xch, &fd) == 2 && (xch == 4 || xch == 8 || xch == 16) && (fd == 0 || (fd >= 2 && fd <= 8)))
-            wide_args = std::to_string(xch) + ", " + std::to_string(fd);
-    }
+    // Template arguments XCH_T, FD_T of its instantiation; they also enter the kernel hash.
+    const std::string wide_args = "16, 2";
     out.hash = fnv1a(gen.body + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
                      "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()) +
                      (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST));
@@ -5629,7 +5504,7 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     // VGPRs, no spill; the three-wave budget measured +1.7 % with 80 spills and was not taken).  Round 5: decay / release /
     // mult are no longer register state (og_nodes.hip.h, EpAmp) -- see scripts/isa_mix.py epiano_voice.  Round 4: with the
     // packed-fma bodies the three-wave budget (168 VGPRs) spills 76 registers, all of them around the chunk loop (25
-    // scratch instructions per 16-frame chunk, none in the frame loop: scripts/isa_mix.py epiano_voice OGC_WAVES_EU=3)
+    // scratch instructions per 16-frame chunk, none in the frame loop: scripts/isa_mix.py epiano_voice)
     // and is 3.3 % faster in an interleaved A/B (1.57e11 -> 1.62e11 at 262 144 voices): taken.  Four waves (128 VGPRs)
     // spill inside the frame loop.
     int waves_eu = (out.lpv > 1 && out.lane_width == 8) ? 3 : 4;
@@ -5638,7 +5513,6 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
         for (const auto& pl : out.players) player_channels += pl.channels;
         if (player_channels > 2) waves_eu = 2;
     }
-    if (const char* ew = ogabi::experiment_knob("OGC_WAVES_EU")) waves_eu = std::max(1, std::min(8, atoi(ew)));
     // the entry points of one kernel shape (`kp`: the kernel name up to the hash): the four ramps / taps variants in the general
     // unit; a zero variant only next to the kernels that read no ramp table (`_00z`, `_01z`)
     auto shape = [&](const std::string& kp, const std::string& fn, int threads, const std::string& attr, const std::string& zattr, const std::string& extra) {
@@ -5653,17 +5527,11 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     std::vector<std::pair<int, int>> depths; // (tag: what OgBlockArgs::split selects, waves per workgroup)
     if (!cg.groups2.empty()) depths.push_back({2, (int)cg.groups2.size()});
     if (!cg.groups4.empty()) depths.push_back({4, (int)cg.groups4.size()});
-    // OGC_NARROW_FD=<depth> (experiment): the 8-frame shapes with the flag hand-off as well, rings of `depth` chunks
-    std::string narrow_args;
-    if (const char* en = ogabi::experiment_knob("OGC_NARROW_FD")) {
-        const int fd = atoi(en);
-        if (fd >= 2 && fd <= 8) narrow_args = ", 8, " + std::to_string(fd);
-    }
     for (auto [K, W] : depths) {
         // (the narrow four-wave form holds six workgroups per CU; left to itself the compiler gives the zero kernel 82 VGPRs
         // where the general one has 80 -- five waves per SIMD.  Held to six: 72 VGPRs, no spill)
-        const std::string zbudget = (K == 4 && narrow_args.empty()) ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
-        shape("og_k" + std::to_string(K) + "_", "voice_block_p" + std::to_string(K), 64 * W, "", zbudget, narrow_args);
+        const std::string zbudget = K == 4 ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
+        shape("og_k" + std::to_string(K) + "_", "voice_block_p" + std::to_string(K), 64 * W, "", zbudget, "");
     }
     if (out.wide4) shape("og_k4w_", "voice_block_p4", 64 * (int)cg.groups4.size(), "", "", ", " + wide_args);
 

@@ -10,7 +10,7 @@ out = ['# Round 6: hand-off of the four-wave kernel -- barrier vs flags, wave pr
        'the chunk\'s values are in registers; `t` = tight poll, no `s_sleep`); `...pr` / `gWXYZ` / `qWXYZ` = flags 16x2 tight with `s_setprio` W,X,Y,Z for the four stages (`h`: 8x4);',
        '`bpr`, `b0123` = the BARRIER with priorities 0,1,1,2 / 0,1,2,3; `d*` = dynamic priority (a wave that had to poll at its chunk top yields) -- rejected; `p*` = progress words',
        'read a chunk ahead -- no gain, removed; `oldtpt*` = round 5\'s TPT update path (not a clean A/B: see ROUND6.md); `flat` = branch-free TPT update on every frame; `cABC` = pipeline',
-       'cut (A,B,C) under flags; `n2` / `n4` = the 8-frame shapes with flags, rings of 2 / 4 (`OGC_NARROW_FD`); `prevhost` = the host library before the ramp-end launch.', '']
+       'cut (A,B,C) under flags; `n2` / `n4` = the 8-frame shapes with flags, rings of 2 / 4 (a generator knob of that round); `prevhost` = the host library before the ramp-end launch.', '']
 for tag in sorted(os.listdir(root)):
     f = os.path.join(root, tag, 'ab.log')
     if not (tag.startswith('r06') or tag.startswith('r07')) or not os.path.exists(f):
