@@ -369,15 +369,27 @@ int og_process_block_async(og_engine* e, uint32_t frames, float* d_out_bus);
  * of n_blocks separate calls, bit for bit; what it saves is n_blocks - 1 crossings of the boundary. */
 int og_process_blocks_async(og_engine* e, uint32_t frames, uint32_t n_blocks, float* d_out_bus, size_t out_stride_bytes);
 int og_synchronize(og_engine* e);
-/* Throughput option for streaming callers of og_process_block_async: up to `blocks` (1..32) consecutive async blocks
+/* Throughput option for streaming callers of og_process_block_async: up to `blocks` (1..256) consecutive async blocks
  * that nothing but event pushes separates (no value change, no taps) are rendered by ONE launch of the voice kernel over
  * their frames back to back -- per-voice state loaded and stored once, one inter-kernel gap, one bus reduce -- instead
  * of a launch each.  The bus of an async block is then complete after the last block of its batch, after og_flush()
  * (launches what is queued, does not wait) or og_synchronize(); every call that reads or changes engine state launches
  * the queue first, and og_process_block / og_render* always deliver complete buses.  Results are those of block-by-block
- * processing, bit for bit.  Default 1 (a launch per block); blocks = 0 picks 8..32 from the bank size (what og_render*
- * and cluster shards use: as many blocks as keep one launch's partial-sum rows within 32 MB).  Measured, fm_voice at
- * 65 536 voices: 1 -> 8 blocks +30 %, 8 -> 32 another +3.5 %. */
+ * processing, bit for bit.  Default 1 (a launch per block).
+ *   blocks = 1..32: the buffers of a launch hold that many full 512-frame blocks.
+ *   blocks = 33..256: a launch also ends where the next block would pass max(16 384, 256 x blocks) frames (a queue of 188
+ *     512-frame blocks goes out as two launches of 94).  A graph whose event handlers read frame_offset takes at most 32
+ *     (OG_E_INVALID above); above 256: OG_E_INVALID.
+ *   blocks = 0 (what og_render* use): 8..32 from the bank size -- as many blocks as keep one launch's partial-sum rows within
+ *     32 MB -- and, for a bank that runs the wide four-wave kernels (every workgroup resident at once), whatever the caller
+ *     queues: up to 256 blocks within 256 MB of partial rows.  Graphs with a post-mix Convolver or with handlers that read
+ *     frame_offset, and cluster shards, stay at 8..32.
+ * Device memory: the partial rows are 4 bytes x frames of a launch x workgroups (64 voices each) x voice channels, allocated
+ * when the setting first needs them and kept: 64 MB at 32 blocks for 65 536 fm_voice voices, 256 MB for that bank's automatic
+ * setting (256 blocks, a capacity of 65 536 frames).
+ * Measured, fm_voice at 65 536 voices: 1 -> 8 blocks +30 %, 8 -> 32 another +3.5 %; 32 -> 188 (one launch for a second of
+ * audio) +2 % with the folded kernels, inside the spread of a run, and +11 % with the general ones
+ * (profiles/r13_launch_length.md). */
 int og_set_bus_batching(og_engine* e, uint32_t blocks);
 int og_flush(og_engine* e);
 int og_set_stream(og_engine* e, void* hip_stream);

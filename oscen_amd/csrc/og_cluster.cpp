@@ -488,8 +488,11 @@ int og_cluster_create(const og_graph_desc* g, uint64_t n_voices_total, const int
             e->bus_stage = false; // shards hand over the voice sum; the post-mix node runs once, on the root
             {
                 HIPCK(hipSetDevice(e->device));
-                e->alloc_bus_buffers(e->auto_batch()); // shards render 8..32 blocks per launch
-                e->bus_batch = e->auto_batch();
+                // shards render 8..32 blocks per launch (their reduce cadence and buffers are built around that, also where a
+                // single engine would take a longer launch)
+                const uint32_t shard_batch = std::min<uint32_t>(e->auto_batch(), OG_MAX_LAUNCH_BLOCKS);
+                e->alloc_bus_buffers(shard_batch);
+                e->bus_batch = shard_batch;
             }
             c->shard.push_back(e.get());
             e.release();

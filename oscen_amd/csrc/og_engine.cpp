@@ -244,7 +244,7 @@ void map_sample_channels(const SampleData& s, uint32_t width, float* dst)
 void og_engine::conv_alloc(size_t need_hist)
 {
     const size_t vc = cg->voice_channels;
-    const size_t max_frames = (size_t)OG_MAX_BLOCK * batch_cap;
+    const size_t max_frames = cap_frames;
     const size_t keep = std::max(hist_keep, (std::max<size_t>(need_hist, 1) + OG_CONV_S - 1) / OG_CONV_S * OG_CONV_S);
     const size_t len = 2 * keep + 2 * max_frames;
     if (!d_hist || keep != hist_keep || len != hist_len) {
@@ -538,8 +538,8 @@ void og_engine::alloc_bus_buffers(uint32_t batch)
             HIPCK(hipFree(*p));
             *p = nullptr;
         }
-    batch_cap = batch;
-    const size_t max_frames = (size_t)OG_MAX_BLOCK * batch;
+    cap_frames = launch_frames_cap(batch);
+    const size_t max_frames = cap_frames;
     const size_t vc = cg->voice_channels; // a Frame<2> voice output: two planes of partial rows
     HIPCK(hipMalloc(&d_partials, (size_t)n_wg * max_frames * 4 * vc));
     HIPCK(hipMemset(d_partials, 0, (size_t)n_wg * max_frames * 4 * vc));
@@ -565,6 +565,8 @@ void og_engine::process_async(uint32_t frames, float* d_out)
     // events wait on the host until the queue is launched: launch it before they outgrow the staging buffers (or the
     // size up to which per-voice segments beat a rebuild of the whole timeline)
     if (!queue.empty() && tl.n_pending() > std::min<size_t>(tl.stage_events() / 2, (size_t)V / 4 + 32)) flush_bus();
+    // the buffers hold cap_frames frames per launch (a queue of up to 32 blocks never reaches this: its capacity is 32 full blocks)
+    if (!queue.empty() && (size_t)q_frames + frames > cap_frames) flush_bus();
     if (queue.empty()) {
         q_frame0 = frame_now;
         q_frames = 0;
@@ -574,7 +576,7 @@ void og_engine::process_async(uint32_t frames, float* d_out)
     // tick_ramps (codegen/mod.rs:878-914): the value seen by frame f is the one after f+1 ticks.  The same
     // per-frame table carries the graph's stream inputs (`<stream_in>_block`, one row each, broadcast to every
     // voice); a graph with stream inputs always runs the table-reading kernel variant.
-    const size_t stride = (size_t)OG_MAX_BLOCK * batch_cap;
+    const size_t stride = cap_frames;
     const bool ramping = active_ramps > 0 && cg->n_ramps > 0;
     if ((ramping || cg->n_streams > 0 || q_ramps) && cg->n_ramps + cg->n_streams > 0) {
         if (q_ramp_slot < 0) { // first block of the queue that needs the table: earlier blocks get constant rows
@@ -650,7 +652,7 @@ void og_engine::flush_bus()
     memset(&A, 0, sizeof A);
     A.n_voices = V;
     A.frames = q_frames;
-    A.ramp_stride = (uint32_t)((size_t)OG_MAX_BLOCK * batch_cap);
+    A.ramp_stride = (uint32_t)cap_frames;
     A.lanes = lanes;
     A.split = split;
     A.wide = wide ? 1u : 0u;
@@ -1939,12 +1941,16 @@ int og_synchronize(og_engine* e)
 int og_set_bus_batching(og_engine* e, uint32_t blocks)
 {
     if (!e) return set_err(OG_E_INVALID, "null engine");
-    if (blocks > OG_MAX_LAUNCH_BLOCKS) return set_err(OG_E_INVALID, "bus batching: 0 (automatic) or 1..32 blocks");
+    if (blocks > OG_MAX_QUEUE_BLOCKS)
+        return set_err(OG_E_INVALID, "bus batching: 0 (automatic) or 1.." + std::to_string(OG_MAX_QUEUE_BLOCKS) + " blocks");
+    if (blocks > OG_MAX_LAUNCH_BLOCKS && e->cg->reads_block_starts) // (the launch carries OG_MAX_LAUNCH_BLOCKS block starts)
+        return set_err(OG_E_INVALID, "bus batching: a graph whose event handlers read frame_offset takes 0 (automatic) or 1.." +
+                                         std::to_string(OG_MAX_LAUNCH_BLOCKS) + " blocks");
     if (blocks == 0) blocks = e->auto_batch();
     return guard([&] {
         HIPCK(hipSetDevice(e->device));
         e->flush_bus();
-        if (blocks > e->batch_cap) e->alloc_bus_buffers(blocks);
+        if (e->launch_frames_cap(blocks) > e->cap_frames) e->alloc_bus_buffers(blocks);
         e->bus_batch = blocks;
         return OG_OK;
     });
@@ -2024,7 +2030,7 @@ int og_render(og_engine* e, uint64_t total_frames, uint32_t block, float* out_bu
         // an offline render has nothing between its blocks: several per launch (the caller's setting is restored)
         e->flush_bus();
         const uint32_t user_batch = e->bus_batch;
-        if (e->batch_cap < e->auto_batch()) e->alloc_bus_buffers(e->auto_batch());
+        if (e->cap_frames < e->launch_frames_cap(e->auto_batch())) e->alloc_bus_buffers(e->auto_batch());
         e->bus_batch = e->auto_batch();
         struct Restore {
             og_engine* e;
@@ -2095,7 +2101,7 @@ int og_render_inputs(og_engine* e, const float* const* inputs, const uint64_t* i
         HIPCK(hipMalloc(&d_all, (size_t)total * ch * 4));
         e->flush_bus();
         const uint32_t user_batch = e->bus_batch;
-        if (e->batch_cap < e->auto_batch()) e->alloc_bus_buffers(e->auto_batch());
+        if (e->cap_frames < e->launch_frames_cap(e->auto_batch())) e->alloc_bus_buffers(e->auto_batch());
         e->bus_batch = e->auto_batch();
         struct Restore {
             og_engine* e;

@@ -163,6 +163,10 @@ struct Ramp { // ValueRampState  oscen-lib/src/graph/types.rs:300-373
 };
 
 constexpr int RAMP_RING = 8;
+// Host-side bounds of one launch of queued blocks (og_set_bus_batching).  OG_MAX_LAUNCH_BLOCKS (32, og_kernel_rt.hip.h) stays
+// the bound for graphs that read block starts on the device.
+constexpr uint32_t OG_MAX_QUEUE_BLOCKS = 256;               // blocks one launch may cover
+constexpr size_t OG_WIDE_ROW_BUDGET = (size_t)256 << 20;    // partial rows of one automatic launch of the wide four-wave form
 constexpr int EV_RING = 8;              // pinned staging buffers of the incremental event path
 
 struct og_graph_desc {
@@ -413,8 +417,12 @@ struct og_engine {
     // A queued block has had its ramps ticked and its stream samples captured; anything that touches engine state
     // launches the queue first.  Results are those of block-by-block processing, bit for bit.
     std::vector<uint32_t> tap_voices; // og_set_voice_taps: the tapped voices by the caller's numbers (slots are resolved from them)
+    // The queue is also bounded in FRAMES (`cap_frames`): the partial rows, the staging bus, the convolver rows and the ramp
+    // tables are sized by it, and a block that would not fit launches the queue first.  Up to OG_MAX_LAUNCH_BLOCKS blocks the
+    // capacity is that of full 512-frame blocks, so a frame bound never cuts such a queue; longer queues are sized for
+    // 256-frame blocks (launch_frames_cap).
     uint32_t bus_batch = 1; // queue limit (blocks per launch)
-    uint32_t batch_cap = 1; // what the buffers are sized for
+    size_t cap_frames = OG_MAX_BLOCK; // frames one launch may cover: what the buffers are sized for
     struct QueuedBlock {
         float* dst; // where the block's bus goes
         uint32_t frames;
@@ -534,12 +542,35 @@ struct og_engine {
     // Blocks per launch for throughput callers (og_render*, cluster shards, og_set_bus_batching(e, 0)): as many as the
     // launch overhead still pays for while the launch's partial-sum rows stay modest.  Measured: fm_voice at 65 536 voices
     // gains 30 % from 1 -> 8 blocks and 3.5 % more from 8 -> 32 (32 MB of rows); sat4x_voice at 131 072 voices and sub_voice
-    // at 262 144 LOSE 10-25 % once the rows of one launch pass ~64 MB, with either row layout (not understood further).
+    // at 262 144 LOSE 10-25 % once the rows of one launch pass ~64 MB, with either row layout (not understood further; those
+    // banks run in several rounds of workgroups, where a longer launch makes the last round's tail longer).  The wide
+    // four-wave form (`wide`: every workgroup resident in one round) is the other way round: a launch there takes everything
+    // the caller queued, up to OG_MAX_QUEUE_BLOCKS blocks within OG_WIDE_ROW_BUDGET of rows -- fm_voice at 65 536 voices, six
+    // launches of 32 blocks against one of 188: +2 % with the folded kernels (inside a run's spread), +11 % with the general
+    // ones; part launch boundaries, part the end of every launch, where its dearest workgroups run on alone
+    // (profiles/r13_launch_length.md).  Kept at 8..32 also there: graphs whose handlers read frame_offset (32 block-start
+    // slots) and graphs with a post-mix Convolver (its rows grow with response x launch length).
     uint32_t auto_batch() const
     {
         const size_t per_block = (size_t)std::max<uint32_t>(n_wg, 1u) * 256u * 4u; // rows of one 256-frame block
+        if (wide && !cg->reads_block_starts && cg->bus_stage != ogc::BusStage::Convolver) {
+            const size_t b = OG_WIDE_ROW_BUDGET / (per_block * std::max<size_t>(cg->voice_channels, 1));
+            return (uint32_t)std::min<size_t>(OG_MAX_QUEUE_BLOCKS, std::max<size_t>(8, b));
+        }
         const size_t b = ((size_t)32 << 20) / per_block;
         return (uint32_t)std::min<size_t>(OG_MAX_LAUNCH_BLOCKS, std::max<size_t>(8, b));
+    }
+    // Frames one launch may cover under a queue limit of `blocks`.  1..32 blocks: full blocks, as ever.  Above: 256-frame
+    // blocks (at 512 the rows of a 256-block queue on 1 024 workgroups would be 0.5 GB), never less than 32 full blocks.
+    // The kernels themselves count frames, chunks and hand-off words in 32 bits and event offsets in 64; the one 32-bit
+    // product on the way is OgBlockArgs::partial_plane (frames rounded to 16 x workgroups), which a Frame<2> bank reads.
+    size_t launch_frames_cap(uint32_t blocks) const
+    {
+        if (blocks <= OG_MAX_LAUNCH_BLOCKS) return (size_t)OG_MAX_BLOCK * blocks;
+        size_t f = std::max<size_t>(OG_MAX_LAUNCH_FRAMES, (size_t)256 * blocks);
+        const size_t plane = (size_t)0xFFFFFFFFu / std::max<uint32_t>(n_wg, 1u) / OG_BUS_CHUNK * OG_BUS_CHUNK;
+        if (cg->voice_channels > 1) f = std::max<size_t>(OG_MAX_LAUNCH_FRAMES, std::min(f, plane));
+        return f;
     }
     // Everything before this frame has been consumed on the device by the time an update issued now takes effect:
     // launched blocks run before it in stream order; blocks still in the queue have not seen their events yet.

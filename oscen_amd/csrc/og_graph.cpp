@@ -5533,6 +5533,7 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
         const std::string zbudget = K == 4 ? " __attribute__((amdgpu_waves_per_eu(6)))" : "";
         shape("og_k" + std::to_string(K) + "_", "voice_block_p" + std::to_string(K), 64 * W, "", zbudget, "");
     }
+    out.reads_block_starts = cg.blk_slot0 >= 0;
     if (out.wide4) shape("og_k4w_", "voice_block_p4", 64 * (int)cg.groups4.size(), "", "", ", " + wide_args);
 
     for (Unit& u : units)

@@ -154,6 +154,7 @@ struct CompiledGraph {
     };
     std::vector<PlayerSpec> players;
     int player_slot0 = -1;
+    bool reads_block_starts = false;   // an event handler reads frame_offset: a launch carries the starts of its (at most 32) blocks
     int lpv = 1;                       // lanes per voice (8 for the electric-piano voice)
     int lane_width = 1;                // words a lane owns of every lane_state array (OG_HPL = 4 when lpv > 1)
     bool can_split = false;            // a two-wave pipeline variant of the kernel exists (og_k2_*)
