@@ -490,6 +490,9 @@ struct Codegen {
         // during the previous outer tick; the producer's queue is cleared there, not per inner tick
         std::ostringstream s_ev6a, s_ev6a_clear;
         std::map<int, std::ostringstream> ev_handlers; // per graph event input
+        // per-voice value input -> the RingPre of every Delay of this stage whose delay_samples or feedback depends on it: a
+        // set-value event on that input ends the chunk's fast path (emit_delay)
+        std::map<int, std::vector<std::string>> ring_pre_of_input;
     };
     Sect sec[16];
     int cs = 0;  // stage being emitted
@@ -1590,6 +1593,15 @@ void emit_delay(NodeCtx& x)
                          << (hint_input ? ds.e : dsv) << ", " << ((x.connected("feedback") && block_const(fb)) ? fb.e : fbv)
                          << ", " << (fixed ? "true" : "false") << ", " << wp << ", " << pre << ", ring_lds[" << K
                          << "], c.lane, base + OG_BUS_CHUNK < A.frames);\n";
+    // `fixed` holds between set-value events only: an event on a per-voice input that either parameter depends on lands
+    // inside a chunk, after ring_chunk_begin has looked at the old values.  The lane it lands on leaves the fast path for
+    // the rest of that chunk (the event walk clears `fast`); the staged column stays as a prediction, which the checked
+    // path of og::delay_tick verifies against the new offset on every tick.
+    std::set<int> vins;
+    if (x.connected("delay_samples")) vins.insert(ds.voice_inputs.begin(), ds.voice_inputs.end());
+    if (x.connected("feedback")) vins.insert(fb.voice_inputs.begin(), fb.voice_inputs.end());
+    if (fixed) // (otherwise `fast` is never set)
+        for (int i : vins) x.cg.S().ring_pre_of_input[i].push_back(pre);
     x.set_out("output", "og::delay_tick(A.rings[" + K + "], A.ring_cap[" + K + "], A.n_voices, c.v, c.valid, " + in.e + ", " +
                             dsv + ", " + fbv + ", " + wp + ", " + fc + ", " + pre + ", ring_lds[" + K + "], c.lane, f - cbase)");
 }
@@ -4358,8 +4370,14 @@ std::string BodyWriter::events_code(const std::vector<int>& stages, bool prefetc
         for (size_t i = 0; i < out.inputs.size(); ++i) {
             const InputInfo& in = out.inputs[i];
             if (in.decl.kind == Kind::Value && in.decl.per_voice) {
+                std::string unfast; // Delay parameters fed by this input: the chunk's staging decision no longer holds
+                for (int st : stages) {
+                    auto it = cg.sec[st].ring_pre_of_input.find((int)i);
+                    if (it == cg.sec[st].ring_pre_of_input.end()) continue;
+                    for (const std::string& pre : it->second) unfast += " " + pre + ".fast = false;";
+                }
                 t << "                " << (first ? "" : "else ") << "if (ev.target == (OG_EV_SETVALUE | " << i
-                  << "u)) { vin_" << i << " = ev.value; derive(); }\n";
+                  << "u)) { vin_" << i << " = ev.value; derive();" << unfast << " }\n";
                 first = false;
             }
         }
