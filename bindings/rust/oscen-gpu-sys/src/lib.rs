@@ -91,6 +91,11 @@ extern "C" {
 #[repr(C)] pub struct og_cluster { _p: [u8; 0] }
 #[repr(C)] pub struct og_node_port { pub name: *const c_char, pub kind: c_int, pub default_value: c_float, pub ctor_arg: c_int, pub channels: u32 }
 #[repr(C)] pub struct og_node_field { pub name: *const c_char, pub is_uint: c_int, pub init: c_float, pub init_uint: u32, pub ctor_arg: c_int }
+/// a per-voice array field of a node type (`buf: [f32; N]`): `og::NodeArray<T, N>& name` in the device source
+#[repr(C)] pub struct og_node_array { pub name: *const c_char, pub length: u32, pub is_uint: c_int, pub init: c_float, pub init_uint: u32 }
+pub const OG_NODE_ARRAY_MAX_LEN: u32 = 65536;
+pub const OG_NODE_ARRAYS_MAX: u32 = 8;
+pub const OG_NODE_ARRAY_WORDS_MAX: u32 = 1 << 20;
 #[repr(C)] pub struct og_node_type {
     pub type_ctor: *const c_char, pub n_ctor_args: u32,
     pub inputs: *const og_node_port, pub n_inputs: u32,
@@ -100,6 +105,7 @@ extern "C" {
     pub event_outputs: *const *const c_char, pub n_event_outputs: u32,
     pub output_channels: *const u32,
     pub event_queue_capacity: u32,
+    pub arrays: *const og_node_array, pub n_arrays: u32,
 }
 extern "C" {
     pub fn og_graph_add_node_array(g: *mut og_graph_desc, name: *const c_char, type_ctor: *const c_char,
@@ -163,6 +169,9 @@ extern "C" {
 extern "C" {
     pub fn og_state_field_index(e: *const og_engine, path: *const c_char) -> c_int;
     pub fn og_read_state_field(e: *mut og_engine, path: *const c_char, first_voice: u32, n: u32, out: *mut c_void) -> c_int;
+    pub fn og_node_array_info(e: *const og_engine, path: *const c_char, length: *mut u32, is_uint: *mut c_int) -> c_int;
+    pub fn og_read_node_array(e: *mut og_engine, path: *const c_char, first_voice: u32, count: u32, out: *mut c_void) -> c_int;
+    pub fn og_write_node_array(e: *mut og_engine, path: *const c_char, first_voice: u32, count: u32, data: *const c_void) -> c_int;
 }
 extern "C" {
     pub fn og_cluster_read_output_events(c: *mut og_cluster, buf: *mut og_out_event, cap: u32, n: *mut u32, n_overflowed: *mut u64) -> c_int;

@@ -219,6 +219,54 @@ pub fn register_function(name: &str, args: &[(&str, u32)], result_channels: u32,
     ck(unsafe { sys::og_register_function(&f) }).map(|_| ())
 }
 
+/// A custom node type (`#[derive(Node)]` struct) as og_register_node takes it.  `arrays` are the struct's `[f32; N]` /
+/// `[u32; N]` fields: per-voice device memory the bodies reach through `name.get(i)`, `name.set(i, x)`, `name.length()`
+/// (an index past the end is clamped to the last element).
+#[derive(Default)]
+pub struct NodeDesc<'a> {
+    pub type_ctor: &'a str,
+    pub n_ctor_args: u32,
+    /// (name, kind: 0 value / 1 event / 2 stream, default, constructor argument or -1, channels)
+    pub inputs: &'a [(&'a str, i32, f32, i32, u32)],
+    pub outputs: &'a [&'a str],
+    /// (name, is_uint, f32 init, u32 init, constructor argument or -1)
+    pub state: &'a [(&'a str, bool, f32, u32, i32)],
+    /// (name, length, is_uint, f32 init, u32 init)
+    pub arrays: &'a [(&'a str, u32, bool, f32, u32)],
+    pub process: &'a str,
+    /// (event input, body of on_<input>())
+    pub handlers: &'a [(&'a str, &'a str)],
+}
+pub fn register_node(d: &NodeDesc) -> Result<(), GpuError> {
+    let cs = |s: &str| CString::new(s).unwrap();
+    let (c_type, c_process) = (cs(d.type_ctor), cs(d.process));
+    let in_names: Vec<CString> = d.inputs.iter().map(|p| cs(p.0)).collect();
+    let ports: Vec<sys::og_node_port> = d.inputs.iter().zip(&in_names)
+        .map(|(p, n)| sys::og_node_port { name: n.as_ptr(), kind: p.1, default_value: p.2, ctor_arg: p.3, channels: p.4 }).collect();
+    let out_names: Vec<CString> = d.outputs.iter().map(|o| cs(*o)).collect();
+    let out_ptrs: Vec<*const std::os::raw::c_char> = out_names.iter().map(|n| n.as_ptr()).collect();
+    let st_names: Vec<CString> = d.state.iter().map(|f| cs(f.0)).collect();
+    let fields: Vec<sys::og_node_field> = d.state.iter().zip(&st_names)
+        .map(|(f, n)| sys::og_node_field { name: n.as_ptr(), is_uint: f.1 as i32, init: f.2, init_uint: f.3, ctor_arg: f.4 }).collect();
+    let arr_names: Vec<CString> = d.arrays.iter().map(|a| cs(a.0)).collect();
+    let arrays: Vec<sys::og_node_array> = d.arrays.iter().zip(&arr_names)
+        .map(|(a, n)| sys::og_node_array { name: n.as_ptr(), length: a.1, is_uint: a.2 as i32, init: a.3, init_uint: a.4 }).collect();
+    let bodies: Vec<Option<CString>> = d.inputs.iter().map(|p| d.handlers.iter().find(|h| h.0 == p.0).map(|h| cs(h.1))).collect();
+    let body_ptrs: Vec<*const std::os::raw::c_char> = bodies.iter().map(|b| b.as_ref().map_or(std::ptr::null(), |c| c.as_ptr())).collect();
+    let t = sys::og_node_type {
+        type_ctor: c_type.as_ptr(), n_ctor_args: d.n_ctor_args, inputs: ports.as_ptr(), n_inputs: ports.len() as u32,
+        outputs: out_ptrs.as_ptr(), n_outputs: out_ptrs.len() as u32, state: fields.as_ptr(), n_state: fields.len() as u32,
+        process_src: c_process.as_ptr(), event_handler_src: body_ptrs.as_ptr(), cost_hint: 0,
+        event_outputs: std::ptr::null(), n_event_outputs: 0, output_channels: std::ptr::null(), event_queue_capacity: 0,
+        arrays: arrays.as_ptr(), n_arrays: arrays.len() as u32,
+    };
+    ck(unsafe { sys::og_register_node(&t) }).map(|_| ())
+}
+pub fn unregister_node(type_ctor: &str) -> Result<(), GpuError> {
+    let c = CString::new(type_ctor).unwrap();
+    ck(unsafe { sys::og_unregister_node(c.as_ptr()) }).map(|_| ())
+}
+
 /// An impulse response as an ASSET (the reference's `external ir: AudioAsset; ir -> reverb.ir;`): `channels` (1..8)
 /// interleaved channels at `sample_rate`.  `GpuGraph::set_bus_ir` conforms it to the engine's rate and maps its channels
 /// onto the bus's, as ConvolverConsumer::build does.
@@ -274,6 +322,30 @@ impl<const IN: usize> GpuGraph<IN> {
         let mut out = vec![0.0f32; n as usize];
         ck(unsafe { sys::og_read_state_field(self.e, c_path.as_ptr(), first_voice, n, out.as_mut_ptr().cast()) })?;
         Ok(out)
+    }
+    /// (length, is_uint) of an array field of a registered node type: "node.field", "array[k].field", "nested.node.field"
+    pub fn node_array_info(&self, path: &str) -> Result<(u32, bool), GpuError> {
+        let c_path = CString::new(path).unwrap();
+        let (mut length, mut is_uint) = (0u32, 0i32);
+        ck(unsafe { sys::og_node_array_info(self.e, c_path.as_ptr(), &mut length, &mut is_uint) })?;
+        Ok((length, is_uint != 0))
+    }
+    /// the field of voices `first_voice .. first_voice + count` as 32-bit words, [count][length] (f32 fields: `f32::from_bits`)
+    pub fn read_node_array(&mut self, path: &str, first_voice: u32, count: u32) -> Result<Vec<u32>, GpuError> {
+        let (length, _) = self.node_array_info(path)?;
+        let c_path = CString::new(path).unwrap();
+        let mut out = vec![0u32; count as usize * length as usize];
+        ck(unsafe { sys::og_read_node_array(self.e, c_path.as_ptr(), first_voice, count, out.as_mut_ptr().cast()) })?;
+        Ok(out)
+    }
+    /// write whole rows ([count][length] words) behind the blocks already queued: a table per voice
+    pub fn write_node_array(&mut self, path: &str, first_voice: u32, rows: &[u32]) -> Result<(), GpuError> {
+        let (length, _) = self.node_array_info(path)?;
+        if length == 0 || rows.len() % length as usize != 0 { // (refused here, where the slice's length is still known)
+            return Err(GpuError(-1, format!("write_node_array: {} words are not whole rows of {} elements", rows.len(), length)));
+        }
+        let c_path = CString::new(path).unwrap();
+        ck(unsafe { sys::og_write_node_array(self.e, c_path.as_ptr(), first_voice, (rows.len() / length as usize) as u32, rows.as_ptr().cast()) }).map(|_| ())
     }
     /// the events the voices pushed into the graph's event outputs since the last call, ordered by (frame, voice, push
     /// order) -- what iterating `graph.<event_output>` gives after process_block -- and how many the log could not hold

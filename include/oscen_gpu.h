@@ -104,6 +104,23 @@ typedef struct {
     uint32_t init_uint; /* ... of a u32 field */
     int ctor_arg;       /* f32 fields: constructor argument that initialises it, or -1 */
 } og_node_field;
+/* A per-voice ARRAY field (`buf: [f32; N]`: a delay line, a history, a table).  process() and every handler see it as
+ * `og::NodeArray<float, N>& <name>` (u32 elements: `og::NodeArray<uint32_t, N>&`), after the scalar state fields:
+ *   name.get(i)     element i            name.set(i, x)   writes element i          name.length()   N, a constant expression
+ * An index >= N is CLAMPED to N - 1, for reads and writes alike (no wrap: write `i & (name.length() - 1)` or `% n`
+ * yourself) -- a stray index never leaves the voice's own planes.  A get(i) after a set(i, x) returns x, within a tick,
+ * within a handler and across the ticks of a launch.  The elements live in device memory (og_node_array.hip.h: element i
+ * of voice slot v at pool[(base + i) * n_voices + v]), persist like any state, and every og_init sets them to `init`. */
+typedef struct {
+    const char* name;      /* identifier; unique among the type's inputs, outputs, state fields and arrays */
+    uint32_t length;       /* elements per voice, 1 .. OG_NODE_ARRAY_MAX_LEN */
+    int is_uint;           /* 0: f32 elements, 1: u32 elements */
+    float init;            /* every element of an f32 array after og_init ... */
+    uint32_t init_uint;    /* ... of a u32 array */
+} og_node_array;
+#define OG_NODE_ARRAY_MAX_LEN 65536u
+#define OG_NODE_ARRAYS_MAX 8u
+#define OG_NODE_ARRAY_WORDS_MAX (1u << 20) /* array words per voice, summed over a graph */
 typedef struct {
     const char* type_ctor; /* "FmOperator::new" */
     uint32_t n_ctor_args;
@@ -132,6 +149,11 @@ typedef struct {
                                             * ArrayVec<EventInstance, 32> (graph/types.rs:18).  The queue lives in
                                             * registers: a graph's kernel is built for the largest capacity among its
                                             * node types (that many VGPRs per event output). */
+    const og_node_array* arrays;           /* per-voice array fields (or NULL): copied by og_register_node */
+    uint32_t n_arrays;                     /* at most OG_NODE_ARRAYS_MAX.  OG_E_INVALID: a bad or duplicate name, length 0,
+                                            * too many arrays; OG_E_UNSUPPORTED: a length above OG_NODE_ARRAY_MAX_LEN, a graph
+                                            * with more than OG_NODE_ARRAY_WORDS_MAX array words per voice, or such a node
+                                            * inside an array-valued voice. */
 } og_node_type;
 #define OG_NODE_EVENTS_PER_FRAME 2
 #define OG_NODE_EVENTS_MAX 32
@@ -419,6 +441,16 @@ int og_render_inputs(og_engine* e, const float* const* inputs, const uint64_t* i
  * the plane number or -1. */
 int og_state_field_index(const og_engine* e, const char* path);
 int og_read_state_field(og_engine* e, const char* path, uint32_t first_voice, uint32_t n, void* out);
+/* The ARRAY fields of registered node types (og_node_array).  path = "<node>.<field>", "<array>[k].<field>" for an element of
+ * a node array, "nested.node.field" as above.  og_node_array_info: the field's length and element type.  og_read_node_array:
+ * out[count][length] receives the arrays of voices first_voice .. (4-byte words: floats or integers); it launches queued
+ * blocks first and waits for the device.  og_write_node_array: the other way round -- queued blocks are launched first and
+ * keep what they were queued under, so a write always falls on a launch boundary (a wavetable per voice, a tuning table per
+ * voice).  Voices are the caller's numbers (og_group_voices).  OG_E_INVALID: null arguments, an unknown path, a voice range
+ * past the bank. */
+int og_node_array_info(const og_engine* e, const char* path, uint32_t* length, int* is_uint);
+int og_read_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, void* out);
+int og_write_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, const void* data);
 
 /* Introspection of `graph.voices[i].<out>` (tests poke node fields in the
  * reference): record the per-voice output of the listed voices during the

@@ -10,6 +10,8 @@
 #include "og_math.h"
 #include "og_bus_conv.hip.h"
 #include "og_asset_resample.hip.h"
+#define OG_NODE_ARRAY_FILL_KERNEL 1
+#include "og_node_array.hip.h"
 
 // Sum the per-workgroup partial rows (fixed association, no atomics).
 // One workgroup per 16 frames, 64 row-slices x 16 frames = 1024 threads: thread (slice s, frame f) adds
@@ -397,6 +399,7 @@ og_engine::~og_engine()
     (void)hipFree(d_bus);
     (void)hipFree(d_taps);
     (void)hipFree(d_tap_slot);
+    (void)hipFree(d_narr);
     (void)hipFree(d_out_ev);
     (void)hipFree(d_out_ev_count);
     for (int i = 0; i < RAMP_RING; ++i) {
@@ -414,6 +417,17 @@ og_engine::~og_engine()
     for (auto ev : t_start) (void)hipEventDestroy(ev);
     for (auto ev : t_stop) (void)hipEventDestroy(ev);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
+}
+
+void og_engine::narr_fill()
+{
+    for (const auto& f : cg->arrays) {
+        const size_t n = (size_t)f.length * V;
+        const size_t threads = std::max<size_t>(3, (n + 3) / 4); // (og_node_array_fill: the 16-byte body and up to 3 words at either end)
+        hipLaunchKernelGGL(og_node_array_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d_narr + (size_t)f.base * V, n, f.init);
+        HIPCK(hipGetLastError());
+    }
+    narr_dirty = false;
 }
 
 void og_engine::upload_initial_state()
@@ -448,6 +462,7 @@ void og_engine::upload_initial_state()
         }
         HIPCK(hipMemsetAsync(d_ring[k], 0, (size_t)cap * V * 4, stream));
     }
+    narr_fill(); // every array field of a registered node type holds its `init`
     HIPCK(hipStreamSynchronize(stream));
 }
 
@@ -697,6 +712,10 @@ void og_engine::flush_bus()
         ps[2] = (uint32_t)((uintptr_t)d_desc & 0xFFFFFFFFu);
         ps[3] = (uint32_t)((uint64_t)(uintptr_t)d_desc >> 32);
         ps[4] = sample_cap;
+    }
+    if (cg->narr_slot0 >= 0) { // array fields of registered node types: the pool (og_node_array.hip.h)
+        A.slots[cg->narr_slot0] = (uint32_t)((uintptr_t)d_narr & 0xFFFFFFFFu);
+        A.slots[cg->narr_slot0 + 1] = (uint32_t)((uint64_t)(uintptr_t)d_narr >> 32);
     }
     if (rcp_cover(release_need(A.slots))) {
         A.rcp_tab = d_rcp;
@@ -1031,6 +1050,7 @@ int og_register_node(const og_node_type* t)
         u.weight = (int)t->cost_hint;
         if (t->event_queue_capacity > 32) throw std::runtime_error("event_queue_capacity: at most 32 (the reference's ArrayVec<EventInstance, 32>)");
         u.event_capacity = (int)t->event_queue_capacity;
+        ognarr::copy_arrays(t->arrays, t->n_arrays, u.arrays);
         ogc::register_user_node(u);
         return OG_OK;
     });
@@ -1433,6 +1453,15 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             // (+ one wave's worth of lane words behind the last plane: OgBlockArgs::lane_dump, where a lane beyond the last
             //  voice writes what an event handler of an array-valued node writes through its state planes)
             HIPCK(hipMalloc(&e->d_lane_state, cg.lane_state.size() * (size_t)n_voices * cg.lpv * cg.lane_width * 4 + (size_t)OG_WAVE * OG_LANE_DUMP_WORDS * 4));
+        if (!cg.arrays.empty()) { // the node-array pool: every array field of every voice
+            const size_t bytes = e->narr_bytes();
+            if (hipMalloc(&e->d_narr, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                e->d_narr = nullptr;
+                throw ogabi::Error(OG_E_NOMEM, "og_create: the array fields of this graph need a pool of " + std::to_string(bytes) + " bytes for " +
+                                                   std::to_string(n_voices) + " voices (" + std::to_string(cg.array_words()) + " words per voice), which the device cannot provide");
+            }
+        }
         if (cg.bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&e->d_bus_phase, 4));
         if (cg.bus_stage == ogc::BusStage::Convolver) // Convolver::with_ir(..) / ::new(): the empty response
             e->conv.cur = e->conv_upload(cg.bus_ir ? cg.bus_ir->data() : nullptr, cg.bus_ir ? cg.bus_ir->size() : 0);
@@ -2179,6 +2208,58 @@ int og_read_state_field(og_engine* e, const char* path, uint32_t first_voice, ui
     });
 }
 
+// ---- array fields of registered node types (og_node_array.hip.h; host bookkeeping: og_node_array_host.h) ---------------------
+int og_node_array_info(const og_engine* e, const char* path, uint32_t* length, int* is_uint)
+{
+    if (!e || !path) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        const int k = ognarr::find_field(e->cg->arrays, path);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no array field '") + path + "'");
+        if (length) *length = e->cg->arrays[k].length;
+        if (is_uint) *is_uint = e->cg->arrays[k].is_uint ? 1 : 0;
+        return OG_OK;
+    });
+}
+
+// the planes of field k <-> the caller's rows; a whole-field transfer (the planes of a field are contiguous, the columns of a
+// voice range are not), then the transposition on the host
+static int node_array_transfer(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, void* out, const void* data)
+{
+    return guard([&]() -> int {
+        const int k = ognarr::find_field(e->cg->arrays, path);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no array field '") + path + "'");
+        if ((uint64_t)first_voice + count > e->V) return set_err(OG_E_INVALID, "voice range out of bounds");
+        HIPCK(hipSetDevice(e->device));
+        e->flush_bus(); // queued blocks keep what they were queued under: a write lands behind them, in stream order
+        const auto& f = e->cg->arrays[k];
+        if (count) {
+            uint32_t* d = e->d_narr + (size_t)f.base * e->V;
+            const size_t bytes = (size_t)f.length * e->V * 4;
+            std::vector<uint32_t> planes((size_t)f.length * e->V);
+            const uint32_t* slot_of = e->phys_of.empty() ? nullptr : e->phys_of.data();
+            if (out || count < e->V) e->bounce.d2h(planes.data(), d, bytes, e->stream);
+            if (out) ognarr::gather_rows(f, e->V, slot_of, first_voice, count, planes.data(), (uint32_t*)out);
+            if (data) {
+                ognarr::scatter_rows(f, e->V, slot_of, first_voice, count, (const uint32_t*)data, planes.data());
+                e->narr_dirty = true;
+                e->bounce.h2d(d, planes.data(), bytes, e->stream);
+            }
+        }
+        HIPCK(hipStreamSynchronize(e->stream));
+        return OG_OK;
+    });
+}
+int og_read_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, void* out)
+{
+    if (!e || !path || (count && !out)) return set_err(OG_E_INVALID, "null argument");
+    return node_array_transfer(e, path, first_voice, count, out, nullptr);
+}
+int og_write_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, const void* data)
+{
+    if (!e || !path || (count && !data)) return set_err(OG_E_INVALID, "null argument");
+    return node_array_transfer(e, path, first_voice, count, nullptr, data);
+}
+
 int og_set_voice_taps(og_engine* e, const uint32_t* voices, uint32_t n)
 {
     if (!e || (n && !voices)) return set_err(OG_E_INVALID, "null argument");
@@ -2466,6 +2547,17 @@ int og_group_voices(og_engine* e, uint32_t policy)
             HIPCK(hipStreamSynchronize(e->stream));
             for (uint32_t v = 0; v < V; ++v) moved[new_phys[v]] = plane[e->phys(v)];
             e->bounce.h2d(d, moved.data(), (size_t)V * 4, e->stream);
+            HIPCK(hipStreamSynchronize(e->stream));
+        }
+        // ... and so do array fields that were written (og_write_node_array) since og_init; untouched ones hold `init` everywhere
+        for (size_t k = 0; e->narr_dirty && k < e->cg->arrays.size(); ++k) {
+            const auto& f = e->cg->arrays[k];
+            uint32_t* d = e->d_narr + (size_t)f.base * V;
+            std::vector<uint32_t> from((size_t)f.length * V), to((size_t)f.length * V);
+            e->bounce.d2h(from.data(), d, from.size() * 4, e->stream);
+            for (uint32_t i = 0; i < f.length; ++i)
+                for (uint32_t v = 0; v < V; ++v) to[(size_t)i * V + new_phys[v]] = from[(size_t)i * V + e->phys(v)];
+            e->bounce.h2d(d, to.data(), to.size() * 4, e->stream);
             HIPCK(hipStreamSynchronize(e->stream));
         }
         e->tl.remap_pending([&](uint32_t slot) { return new_phys[e->logical(slot)]; });

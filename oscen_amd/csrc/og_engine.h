@@ -24,6 +24,7 @@
 #include "og_abi.h"
 #include "og_graph.h"
 #include "og_jit.h"
+#include "og_node_array_host.h"
 #include "og_registry.h"
 #include "og_timeline.h"
 
@@ -398,6 +399,13 @@ struct og_engine {
             if (cg->players[k].name == p) return (int)k;
         return -1;
     }
+    // ---- array fields of registered node types: the node-array pool (og_node_array.hip.h) ----------------------------------
+    // [cg->array_words()][V] words, allocated by og_create, filled with the fields' `init` by every og_init, handed to the
+    // kernels through two uniform slots per launch
+    uint32_t* d_narr = nullptr;
+    bool narr_dirty = false; // written since the last fill (og_write_node_array, og_load_state): og_group_voices moves the columns
+    size_t narr_bytes() const { return (size_t)ognarr::pool_bytes(cg->arrays, V); }
+    void narr_fill(); // stream-ordered
     OgEvent* d_events = nullptr;
     uint32_t* d_ev_end = nullptr;
     uint32_t* d_ev_cursor = nullptr;

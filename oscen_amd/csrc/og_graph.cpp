@@ -1930,6 +1930,26 @@ void emit_user(NodeCtx& x)
             st.push_back(x.state_f(f.name, [init](const UEnv&) { return init; }));
         }
     }
+    // array fields (og_node_array.hip.h): every instance gets its own planes of the engine's node-array pool; the bodies see
+    // a view per field, formed once per launch
+    for (const UserArray& a : u.arrays) {
+        if (x.cg.out.lpv > 1)
+            fail_unsupported("node '" + x.n.decl->name + "' (" + u.type + "): a node with array fields inside an array-valued voice ([f32; 32] nodes) is not supported in this version");
+        if (x.cg.out.narr_slot0 < 0) { // filled by the engine per launch: the pool's address
+            x.cg.out.narr_slot0 = x.cg.new_slot([](const UEnv&) { return 0u; });
+            (void)x.cg.new_slot([](const UEnv&) { return 0u; });
+            x.cg.common_decl << "    og::narr_word* const narr_pool = og::node_array_pool(A, " << x.cg.out.narr_slot0 << ");\n";
+        }
+        const uint32_t base = x.cg.out.array_words();
+        if ((uint64_t)base + a.length > NODE_ARRAY_WORDS_MAX)
+            fail_unsupported("node '" + x.n.decl->name + "' (" + u.type + "): the array fields of this graph take more than " +
+                             std::to_string(NODE_ARRAY_WORDS_MAX) + " words per voice");
+        x.cg.out.arrays.push_back({x.n.decl->name + "." + a.name, base, a.length, a.is_uint, a.is_uint ? a.init_u : fbits(a.init_f)});
+        const std::string T = std::string(a.is_uint ? "uint32_t" : "float") + ", " + std::to_string(a.length) + "u";
+        x.cg.S().decl << "    og::NodeArray<" << T << "> " << x.p << a.name << " = og::node_array<" << T << ">(narr_pool, " << base
+                      << "u, A.n_voices, c.v, c.valid);\n";
+        st.push_back(x.p + a.name);
+    }
     // EventInstance::frame_offset (graph/types.rs): a handler whose source names `frame_offset` receives the offset of the
     // event inside the process_block call it belongs to, rescaled by N for a node of the oversampled region
     // (compute_event_rescale, ir/lower.rs:846-852; oscen-lib/tests/multirate_graph.rs EventOffsetRescale)
@@ -1977,6 +1997,10 @@ void emit_user(NodeCtx& x)
             for (const UserState& f : u.state) {
                 sep();
                 q << (f.is_uint ? "uint32_t& " : "float& ") << f.name;
+            }
+            for (const UserArray& a : u.arrays) {
+                sep();
+                q << "og::NodeArray<" << (a.is_uint ? "uint32_t" : "float") << ", " << a.length << "u>& " << a.name;
             }
             if (!handler)
                 for (size_t oi = 0; oi < u.outputs.size(); ++oi) {
@@ -2960,6 +2984,14 @@ void register_user_node(const UserNodeType& t)
         uniq(f.name);
         if (f.arg >= (int)t.nargs) fail("node type '" + t.type + "': field '" + f.name + "' refers to a missing constructor argument");
     }
+    if (t.arrays.size() > NODE_ARRAYS_MAX) fail("node type '" + t.type + "': at most " + std::to_string(NODE_ARRAYS_MAX) + " array fields per type");
+    for (const auto& a : t.arrays) {
+        uniq(a.name);
+        if (a.length == 0) fail("node type '" + t.type + "': array field '" + a.name + "' has length 0");
+        if (a.length > NODE_ARRAY_MAX_LEN)
+            fail_unsupported("node type '" + t.type + "': array field '" + a.name + "' has " + std::to_string(a.length) + " elements, at most " +
+                             std::to_string(NODE_ARRAY_MAX_LEN) + " are supported");
+    }
     for (const auto& h : t.handlers) {
         bool ok = false;
         for (const auto& p : t.inputs) ok = ok || (p.kind == Kind::Event && p.name == h.first);
@@ -3926,6 +3958,8 @@ void Lowering::plan_pipeline_stages()
     bool any_delay = false; // delay lines are staged per chunk by the ordinary kernel only
     for (int ni : order) any_delay = any_delay || cg.nodes[ni].decl->type.rfind("Delay::", 0) == 0;
     for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
+    // (array fields of registered node types: one wave stays the sole owner of its voices' planes, og_node_array.hip.h)
+    for (int ni : order) any_delay = any_delay || (cg.nodes[ni].type && cg.nodes[ni].type->user && !cg.nodes[ni].type->user->arrays.empty());
     bool want = cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
                 !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
     // estimated per-tick VALU cost of every node, in emission order
@@ -5449,7 +5483,8 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     const std::string wide_args = "16, 2";
     out.hash = fnv1a(gen.body + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
                      "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()) +
-                     (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST));
+                     (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST) +
+                     (out.arrays.empty() ? std::string() : std::string("|narr") + OG_NARR_DIGEST));
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
 
@@ -5500,7 +5535,8 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     if (out.lpv > 1) pre << "\n#define OG_HPL " << out.lane_width << " // harmonics per lane (OGC_HPL)";
     if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
     pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "")
-        << (out.players.empty() ? "" : "#include \"og_sample_player.hip.h\"\n") << "\n"
+        << (out.players.empty() ? "" : "#include \"og_sample_player.hip.h\"\n")
+        << (out.arrays.empty() ? "" : "#include \"og_node_array.hip.h\"\n") << "\n"
         << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
         << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
         << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"

@@ -154,6 +154,19 @@ struct CompiledGraph {
     };
     std::vector<PlayerSpec> players;
     int player_slot0 = -1;
+    // array fields of registered node types (og_node_array.hip.h): one entry per (node instance, field).  Element i of voice
+    // slot v lives at pool[(base + i) * n_voices + v] of the engine's node-array pool; narr_slot0 is the first of the two
+    // slots the ENGINE fills per launch with the pool's address (no UniformProg)
+    struct ArraySpec {
+        std::string path;  // "node.field" of the flattened graph, as the state words are named
+        uint32_t base = 0; // first plane, in words per voice
+        uint32_t length = 0;
+        bool is_uint = false;
+        uint32_t init = 0; // bits
+    };
+    std::vector<ArraySpec> arrays;
+    int narr_slot0 = -1;
+    uint32_t array_words() const { return arrays.empty() ? 0u : arrays.back().base + arrays.back().length; } // per voice
     bool reads_block_starts = false;   // an event handler reads frame_offset: a launch carries the starts of its (at most 32) blocks
     int lpv = 1;                       // lanes per voice (8 for the electric-piano voice)
     int lane_width = 1;                // words a lane owns of every lane_state array (OG_HPL = 4 when lpv > 1)
@@ -226,6 +239,16 @@ struct UserState {
     uint32_t init_u = 0;
     int arg = -1; // constructor argument that initialises it (f32 fields), or -1
 };
+struct UserArray { // a per-voice array field (og_node_array)
+    std::string name;
+    uint32_t length = 0;
+    bool is_uint = false;
+    float init_f = 0.0f;
+    uint32_t init_u = 0;
+};
+constexpr uint32_t NODE_ARRAY_MAX_LEN = 65536u;       // (OG_NODE_ARRAY_MAX_LEN)
+constexpr uint32_t NODE_ARRAYS_MAX = 8u;              // per type
+constexpr uint32_t NODE_ARRAY_WORDS_MAX = 1u << 20;   // per voice, summed over a graph
 struct UserNodeType {
     std::string type; // "FmOperator::new"
     size_t nargs = 0;
@@ -234,6 +257,7 @@ struct UserNodeType {
     std::vector<int> out_channels;       // per output: 1 = f32, N = Frame<N> (empty: all f32)
     std::vector<std::string> ev_outputs; // `#[output(event)]` fields
     std::vector<UserState> state;
+    std::vector<UserArray> arrays; // `og::NodeArray<T, N>& <name>` in the bodies, after the state fields
     std::string process_src;
     std::map<std::string, std::string> handlers; // event input -> body of on_<input>()
     int weight = 0; // estimated VALU cost per tick (0 = estimate from the source)

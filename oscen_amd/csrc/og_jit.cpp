@@ -43,15 +43,16 @@ std::string slurp(const std::string& path)
 std::vector<char> compile_to_code(const ogc::CompiledGraph& cg, const char* arch)
 {
     const std::string dir = csrc_dir();
-    const char* names[6] = {"og_kernel_rt.hip.h", "og_nodes.hip.h", "og_math.h", "og_adsr_params.hip.h", "og_sample_player.hip.h", "og_stage_uniform.hip.h"};
-    std::string bodies[6];
-    const char* srcs[6];
-    for (int i = 0; i < 6; ++i) {
+    const char* names[7] = {"og_kernel_rt.hip.h", "og_nodes.hip.h", "og_math.h", "og_adsr_params.hip.h", "og_sample_player.hip.h", "og_stage_uniform.hip.h",
+                            "og_node_array.hip.h"};
+    std::string bodies[7];
+    const char* srcs[7];
+    for (int i = 0; i < 7; ++i) {
         bodies[i] = slurp(dir + "/" + names[i]);
         srcs[i] = bodies[i].c_str();
     }
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source + cg.zero2_source).c_str(), (cg.name + ".hip").c_str(), 6, srcs, names) != HIPRTC_SUCCESS)
+    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source + cg.zero2_source).c_str(), (cg.name + ".hip").c_str(), 7, srcs, names) != HIPRTC_SUCCESS)
         throw std::runtime_error("oscen jit: hiprtcCreateProgram failed");
     std::string archopt = std::string("--offload-arch=") + arch;
     const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-DOG_JIT=1"};

@@ -82,10 +82,13 @@ size_t samples_bytes(const og_engine* e)
     return n;
 }
 
+// Array fields of registered node types: a section of their own behind the delay lines, ONLY in blobs of graphs that have
+// such a field -- a head naming the fields' lengths (og_node_array_host.h), then the node-array pool as it lies on the device
+size_t narr_section_bytes(const og_engine* e) { return e->cg->arrays.empty() ? 0 : ognarr::section_head_bytes(e->cg->arrays) + e->narr_bytes(); }
 size_t dsp_bytes(const og_engine* e)
 {
     return (e->cg->state.size() + e->cg->lane_state.size() * e->cg->lpv * e->cg->lane_width) * (size_t)e->V * 4 +
-           (e->cg->bus_stage == ogc::BusStage::Tremolo ? 4 : 0) + e->ring_bytes();
+           (e->cg->bus_stage == ogc::BusStage::Tremolo ? 4 : 0) + e->ring_bytes() + narr_section_bytes(e);
 }
 // Every event that has not fired by frame_now.  Blocks that are still queued (og_set_bus_batching) consume the events
 // in [q_frame0, frame_now) when they are launched, and the snapshot header stores the post-queue frame_now: those
@@ -145,6 +148,12 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
             const size_t n = (size_t)e->ring_cap[k] * e->V * 4;
             if (n) e->bounce.d2h((char*)dst + off, e->d_ring[k], n, e->stream);
             off += n;
+        }
+        if (!e->cg->arrays.empty()) {
+            ognarr::write_section_head(e->cg->arrays, (char*)dst + off);
+            off += ognarr::section_head_bytes(e->cg->arrays);
+            e->bounce.d2h((char*)dst + off, e->d_narr, e->narr_bytes(), e->stream);
+            off += e->narr_bytes();
         }
         HIPCK(hipStreamSynchronize(e->stream));
         char* p = (char*)dst + off;
@@ -207,6 +216,14 @@ int og_load_state(og_engine* e, const void* src, size_t len)
 {
     if (!e || !src) return set_err(OG_E_INVALID, "null argument");
     const size_t dsp = dsp_bytes(e);
+    if (!e->cg->arrays.empty()) { // the node-array section names its fields: checked before anything else is believed
+        const int rc = ogabi::guard([&]() -> int {
+            const size_t at = dsp - narr_section_bytes(e);
+            const std::string bad = ognarr::check_section_head(e->cg->arrays, (const char*)src + std::min(at, len), len > at ? len - at : 0);
+            return bad.empty() ? OG_OK : set_err(OG_E_INVALID, bad);
+        });
+        if (rc != OG_OK) return rc;
+    }
     if (len < dsp + sizeof(SnapHeader)) return set_err(OG_E_INVALID, "state blob size mismatch");
     SnapHeader h;
     memcpy(&h, (const char*)src + dsp, sizeof h);
@@ -353,6 +370,12 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             const size_t n = (size_t)e->ring_cap[k] * e->V * 4;
             if (n) e->bounce.h2d(e->d_ring[k], (const char*)src + off, n, e->stream);
             off += n;
+        }
+        if (!e->cg->arrays.empty()) {
+            off += ognarr::section_head_bytes(e->cg->arrays);
+            e->bounce.h2d(e->d_narr, (const char*)src + off, e->narr_bytes(), e->stream);
+            e->narr_dirty = true;
+            off += e->narr_bytes();
         }
         e->reset_timeline();
         HIPCK(hipStreamSynchronize(e->stream));
