@@ -4994,11 +4994,45 @@ void PipelineWave::checked(const std::string& ind)
     body << bw.fc_sync(st, ind);
     prefetch(ind);
     const std::string flag = std::string("true, true, ") + (pre ? "true" : "false") + ", false";
+    if (!stage_bodies) {
+        body << ind << "#pragma unroll\n"
+             << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
+             << ind << "    const uint32_t f = base + j;\n"
+             << ind << "    if (__any((int)(f == c.next_ev))) events(f); // (wave-uniform: rare)\n"
+             << ind << "    " << call(flag) << "\n"
+             << ind << "}\n";
+        return;
+    }
+    // Quarters (og_stage_uniform.hip.h, "the quiet quarters of a checked chunk", has the argument): outside a note's first
+    // frames a checked chunk holds ONE event or stage end, and the other three quarters of its 16 frames ran 12 event tests and
+    // 12-24 stage-end tests with their joins for nothing.  The chunk is XCH / 4 quarters of four frames; before each one the
+    // wave asks the quiet test's two questions about these four frames only -- on the state the previous quarter left -- and
+    // runs them without the tests where the answer is no.  Both sides are unrolled with a constant `j`; the same tick site, the
+    // same release form (v_rcp_f32 on e.fc, which events and stage ends re-derive).  Wide form only (FD_T != 0: a constant,
+    // so the 8-frame kernels keep their code).
+    const std::string quiet_flag = std::string("false, true, ") + (pre ? "true" : "false") + ", false";
     body << ind << "#pragma unroll\n"
-         << ind << "for (uint32_t j = 0; j < XCH; ++j) {\n"
-         << ind << "    const uint32_t f = base + j;\n"
-         << ind << "    if (__any((int)(f == c.next_ev))) events(f); // (wave-uniform: rare)\n"
-         << ind << "    " << call(flag) << "\n"
+         << ind << "for (uint32_t q = 0; q < XCH / 4u; ++q) {\n"
+         << ind << "    if (FD_T != 0 && __all((int)(c.next_ev >= base + 4u * q + 4u)) && __all((int)(" << mc
+         << " > 4u))) { // a quiet quarter: no event, no stage end in these four frames\n"
+         << ind << "        og::quarter_count<false>(" << gi << "u);\n"
+         << ind << "        #pragma unroll\n"
+         << ind << "        for (uint32_t i = 0; i < 4u; ++i) {\n"
+         << ind << "            const uint32_t j = 4u * q + i, f = base + j;\n"
+         << ind << "            " << call(quiet_flag) << "\n"
+         << ind << "        }\n"
+         << ind << "    } else {\n"
+         << ind << "        og::quarter_count<true>(" << gi << "u);\n"
+         << ind << "        #pragma unroll\n"
+         << ind << "        for (uint32_t i = 0; i < 4u; ++i) {\n"
+         << ind << "            const uint32_t j = 4u * q + i, f = base + j;\n"
+         << ind << "            if (__any((int)(f == c.next_ev))) events(f); // (wave-uniform: rare)\n"
+         << ind << "            " << call(flag) << "\n"
+         // (a stage with several envelopes: with the quarters fm_voice's og_k4w_*_00z2 takes 121 VGPRs, a granule more than its
+         //  `_z` twin; nothing moved across the end of a checked frame -- the next one begins with a branch anyway -- 119)
+         << (envs.size() > 1 ? ind + "            if constexpr (FD_T != 0) og::frame_sched_fence();\n" : std::string())
+         << ind << "        }\n"
+         << ind << "    }\n"
          << ind << "}\n";
 }
 

@@ -45,6 +45,33 @@
 // is stored.
 //
 // OG_STRICT builds keep the general tick in both bodies (its release arithmetic is a different expression).
+//
+// ---- the quiet quarters of a checked chunk (og_graph.cpp, PipelineWave::checked; wide form) ----
+// A chunk with an event or a stage end in ANY lane runs the checked body: per frame f = base + j one wave-uniform event test
+// (`any lane has next_ev == f` -> events(f)) and, per envelope, the tick adsr_tick<true, true> on e.fc followed by the stage-end
+// test (cnt == 0 -> adsr_complete).  The body is cut into quarters of four frames, j = 4q .. 4q + 3, and before quarter q the
+// wave tests, on the state quarter q - 1 left,
+//     (E) in every lane  next_ev >= base + 4q + 4        (M) in every lane, for every envelope of the stage  cnt > 4
+// and where both hold it runs the four frames with the chunk flag BoolC<false, true, pre, false> instead of <true, true, pre,
+// false>, and without the event test.
+// Claim: under (E) and (M) the checked quarter's tests do not fire, so leaving them out leaves the same operations.
+//   Events.  next_ev changes only in events() (og::ev_advance), which the quiet quarter does not call; so next_ev >= base + 4q + 4
+//     > f holds at each of its frames, in every lane: `f == next_ev` is false in every lane and the checked quarter would not
+//     have called events() either.
+//   Stage ends.  cnt changes by the tick's `cnt -= 1` and in adsr_enter(), which only events() and adsr_complete() reach.  With
+//     no events() (above), by induction over the four frames: before frame 4q + i no stage end has fired in this quarter, so cnt
+//     is its value at the test minus i, > 4 - i; after the tick it is > 3 - i >= 0 for i <= 3: not 0, adsr_complete() does
+//     nothing, and the induction goes on.  A holding envelope counts down from ADSR_HOLD = 2^32 - 1 and is re-pinned by
+//     adsr_enter(); it passes (M) for as long as it passes the chunk test's `cnt > XCH`.
+//   The tick.  The flag's `value` guards the stage-end blocks and nothing else; `release`, `pre`, `steady` and `table` are the
+//     same in both flags and neither is a StageC, so both quarters run adsr_tick_chunk<true, false> = adsr_tick<true, true>: the
+//     reciprocal of e.fc and `fc -= 1`.  e.fc == (float)cnt at the chunk's top (the body's first lines) and after every
+//     adsr_enter(); the quiet and the checked quarters step it alike, so it does not matter which kind ran before.
+//   The test is taken again before every quarter.  An event or a completed stage in quarter q - 1 went through adsr_enter(): the
+//     countdown (M) reads before quarter q is the entered stage's real one (a 3-frame attack entered in quarter q - 1 fails (M)
+//     and its end is met in a checked quarter), and next_ev is the lane's following event.
+// Not covered, on purpose: rcp_len, rs and the stage-uniform predicates play no part -- the quarter keeps the checked body's own
+// release form, so a short reciprocal table or a mixed wave changes nothing here.
 #pragma once
 #include "og_nodes.hip.h"
 
@@ -58,6 +85,8 @@
 // loaded, one count per wave and chunk -- a test reads it through the library's handle, like the runtime's C symbols
 extern "C" {
 __attribute__((weak)) unsigned long long og_stage_uniform_chunks[2][8] = {};
+// ... and the quarters of checked chunks run without ([0][stage]) and with ([1][stage]) their tests, one count per wave and quarter
+__attribute__((weak)) unsigned long long og_checked_quarters[2][8] = {};
 }
 #endif
 
@@ -135,6 +164,26 @@ __device__ __forceinline__ void stage_body_count(const uint32_t stage)
 #ifdef OG_HOSTSIM
     static_assert(M == ENV_HOLD || M == ENV_RELEASE, "a stage-uniform body");
     if (threadIdx.x % OG_WAVE == 0u) og_stage_uniform_chunks[M - 1][stage & 7u] += 1ull;
+#else
+    (void)stage;
+#endif
+}
+
+// after a frame of a checked quarter: the instruction scheduler does not move anything across (og_graph.cpp,
+// PipelineWave::checked, says where and why); no instruction of its own
+__device__ __forceinline__ void frame_sched_fence()
+{
+#ifndef OG_HOSTSIM
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
+// host simulator: one count per wave and quarter of a checked chunk (CHECKED = the quarter kept its tests); nothing on the device
+template <bool CHECKED>
+__device__ __forceinline__ void quarter_count(const uint32_t stage)
+{
+#ifdef OG_HOSTSIM
+    if (threadIdx.x % OG_WAVE == 0u) og_checked_quarters[CHECKED ? 1 : 0][stage & 7u] += 1ull;
 #else
     (void)stage;
 #endif
