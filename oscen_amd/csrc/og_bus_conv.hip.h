@@ -35,21 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "og_bus_conv_host.h" // OG_CONV_S, OG_CONV_F, OG_CONV_LANES, OG_CONV_MAX_TAPS, OgConvResponse
 #include "og_math.h"
-
-#define OG_CONV_S 256 // taps per segment
-#define OG_CONV_F 256 // frames per tile
-#define OG_CONV_LANES (OG_CONV_F / 4)
-#define OG_CONV_MAX_TAPS (1u << 20) // 4 096 partial rows per frame at most
-
-struct OgConvResponse {
-    const float* taps; // device: n_taps floats, or -- tap_stride != 0 -- one plane of n_taps floats per channel, tap_stride apart
-    uint32_t n_taps;   // per channel
-    uint32_t n_frames; // frames of the run this response is evaluated for (the fading-out one: up to the end of the fade)
-    int32_t lo;        // first readable sample, relative to the run's first frame: max(history valid from, start of the buffer)
-    uint32_t tap_stride; // floats between the tap planes of two channels; 0: every channel reads the same plane
-    float* rows;       // partial rows [segment][channel][row_stride]
-};
 
 // x: interleaved history, pointing at the run's first frame; sample (f, c) = x[f * channels + c], f may be negative down to r.lo
 __global__ __launch_bounds__(OG_CONV_LANES) void og_bus_conv(const float* __restrict__ x, uint32_t channels, OgConvResponse r, uint32_t row_stride)

@@ -241,38 +241,63 @@ void map_sample_channels(const SampleData& s, uint32_t width, float* dst)
 } // namespace
 
 // ---- og_engine: the methods that launch kernels or use the device headers above ---------------------------------------
-// (re)size the history and the partial rows for responses of up to need_hist + 1 taps and the current batch size,
-// keeping the history; the stream is idle (callers launch the queue and wait first)
-void og_engine::conv_alloc(size_t need_hist)
+// (re)size the history and the partial rows for responses of up to k taps and the current launch capacity, keeping the
+// history; the stream is idle (callers launch the queue and wait first)
+void og_engine::conv_alloc(size_t k)
 {
     const size_t vc = cg->voice_channels;
-    const size_t max_frames = cap_frames;
-    const size_t keep = std::max(hist_keep, (std::max<size_t>(need_hist, 1) + OG_CONV_S - 1) / OG_CONV_S * OG_CONV_S);
-    const size_t len = 2 * keep + 2 * max_frames;
-    if (!d_hist || keep != hist_keep || len != hist_len) {
+    const BusConvolver::Sizing sz = bus_conv.size_for(k, cap_frames, vc);
+    if (sz.new_hist) {
         float* n = nullptr;
-        HIPCK(hipMalloc(&n, len * vc * 4));
-        HIPCK(hipMemsetAsync(n, 0, len * vc * 4, stream));
+        HIPCK(hipMalloc(&n, sz.len * vc * 4));
+        HIPCK(hipMemsetAsync(n, 0, sz.len * vc * 4, stream));
         if (d_hist) {
-            HIPCK(hipMemcpyAsync(n + (keep - hist_keep) * vc, d_hist + (hist_pos - hist_keep) * vc, hist_keep * vc * 4, hipMemcpyDeviceToDevice, stream));
+            HIPCK(hipMemcpyAsync(n + sz.copy_to * vc, d_hist + sz.copy_from * vc, sz.copy_frames * vc * 4, hipMemcpyDeviceToDevice, stream));
             HIPCK(hipStreamSynchronize(stream));
             HIPCK(hipFree(d_hist));
         }
         d_hist = n;
-        hist_keep = keep;
-        hist_len = len;
-        hist_pos = keep;
     }
-    const uint32_t stride = (uint32_t)((max_frames + 3) / 4 * 4);
-    const size_t half = (keep / OG_CONV_S + 1) * vc * stride;
-    if (!d_conv_rows || stride != conv_row_stride || half != conv_rows_half) {
+    if (sz.new_rows) {
         if (d_conv_rows) HIPCK(hipFree(d_conv_rows));
         d_conv_rows = nullptr;
-        HIPCK(hipMalloc(&d_conv_rows, 2 * half * 4));
-        conv_row_stride = stride;
-        conv_rows_half = half;
+        HIPCK(hipMalloc(&d_conv_rows, 2 * sz.rows_half * 4));
     }
+    bus_conv.resized(sz);
     HIPCK(hipStreamSynchronize(stream));
+}
+
+// flush_bus, in front of the bus sum: the dry sum goes behind the history; when the buffer is full the newest frames move
+// to its front first
+float* og_engine::conv_place_dry(BusConvolver::Launch& l)
+{
+    const uint32_t ch = cg->voice_channels;
+    l = bus_conv.plan_launch(q_frame0, q_frames, conv_fade_len());
+    if (l.move) {
+        const uint32_t n = (uint32_t)(l.move_frames * ch);
+        hipLaunchKernelGGL(og_bus_conv_move, dim3((n + 255) / 256), dim3(256), 0, stream, d_hist + l.move_from * ch, d_hist + l.move_to * ch, n);
+    }
+    return d_hist + l.dry_at * ch;
+}
+
+// flush_bus, behind the bus sum: one pass per run of blocks queued under the same responses -- as a rule the whole launch
+void og_engine::conv_stage(BusConvolver::Launch& l, float* wet)
+{
+    const uint32_t ch = cg->voice_channels, row_stride = bus_conv.row_stride();
+    BusConvolver::Run run;
+    while (bus_conv.next_run(l, queue, run)) {
+        run.cur.rows = d_conv_rows;
+        run.old.rows = d_conv_rows + bus_conv.rows_half();
+        const float* x = d_hist + run.x_at * ch;
+        for (const OgConvResponse* r : {&run.cur, &run.old})
+            if (r->n_frames && r->n_taps)
+                hipLaunchKernelGGL(og_bus_conv, dim3((r->n_frames + OG_CONV_F - 1) / OG_CONV_F, (r->n_taps + OG_CONV_S - 1) / OG_CONV_S, ch),
+                                   dim3(OG_CONV_LANES), 0, stream, x, ch, *r, row_stride);
+        hipLaunchKernelGGL(og_bus_conv_finish, dim3((run.nf + 255) / 256, ch), dim3(256), 0, stream, run.cur, run.old, ch, row_stride,
+                           run.fade_pos, run.fade_len, wet + run.f0 * ch);
+    }
+    bus_conv.launched(l);
+    HIPCK(hipGetLastError());
 }
 
 // og_set_bus_ir on an asset response (ConvolverConsumer::build -> MultiConvolverEngine::from_asset, convolution/mod.rs:335-351):
@@ -280,7 +305,7 @@ void og_engine::conv_alloc(size_t need_hist)
 // onto the bus's channels -- a multi-channel response on a mono bus is averaged (to_mono), one source channel is ONE plane
 // shared by every bus channel, otherwise bus channel c takes source channel min(c, channels - 1).  Every check comes before
 // the device is touched; the engine's state is not changed here.  Waits for the stream (the host copy comes back).
-std::shared_ptr<og_engine::ConvIR> og_engine::conv_build_asset(const std::string& name, const ogc::IrAsset& a)
+std::shared_ptr<ConvIR> og_engine::conv_build_asset(const std::string& name, const ogc::IrAsset& a)
 {
     const uint32_t rate = graph_rate("og_set_bus_ir");
     const bool conform = a.rate != rate;
@@ -561,7 +586,7 @@ void og_engine::alloc_bus_buffers(uint32_t batch)
     HIPCK(hipMalloc(&d_partials2, ((size_t)n_wg / OG_RED_GROUP + 2 + 64) * max_frames * 4));
     HIPCK(hipMalloc(&d_stage_bus, max_frames * OG_MAX_BUS_CHANNELS * 4));
     if (cg->bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
-    if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(std::max(conv.cur ? conv.cur->K() : 0u, conv.old ? conv.old->K() : 0u));
+    if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(bus_conv.longest_taps());
     const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
     for (int i = 0; i < RAMP_RING && rows; ++i) {
         if (d_ramp[i]) HIPCK(hipFree(d_ramp[i]));
@@ -626,21 +651,7 @@ void og_engine::process_async(uint32_t frames, float* d_out)
     qb.frames = frames;
     qb.trem_rate = qb.trem_depth = 0.0f;
     qb.conv = 0;
-    if (conv_on()) { // voices.output -> reverb.input; reverb.output -> out
-        // Convolver::process (convolution/mod.rs:535-573): the outgoing response is dropped once pos reaches fade_len; a
-        // swap retires a response that is still fading out at once and fades from the current one, which keeps its history
-        if (conv.old && frame_now >= conv.fade_start + conv_fade_len()) conv_retire(conv.old);
-        if (conv_pending) {
-            conv_retire(conv.old);
-            conv.old = conv.cur;
-            conv.old_from = conv.cur_from;
-            conv.cur = conv_pending;
-            conv.cur_from = conv.fade_start = frame_now;
-            conv_pending.reset();
-        }
-        if (q_conv.empty() || !q_conv.back().same(conv)) q_conv.push_back(conv);
-        qb.conv = (uint32_t)q_conv.size() - 1;
-    }
+    if (conv_on()) qb.conv = bus_conv.queue_block(frame_now, conv_fade_len()); // voices.output -> reverb.input; reverb.output -> out
     if (cg->bus_stage == ogc::BusStage::Tremolo && bus_stage) { // voices.output -> tremolo.input; tremolo.output -> out (Frame<2>)
         ogc::UEnv ev = env();
         qb.trem_rate = cg->tremolo_rate(ev);
@@ -791,14 +802,8 @@ void og_engine::flush_bus()
         contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * ch;
     float* sum_dst = post_mix ? d_mono : (contiguous ? queue[0].dst : d_stage_bus);
     float* const wet_dst = sum_dst;
-    if (post_conv) { // the dry sum goes behind the history; when the buffer is full the newest hist_keep frames move to its front
-        if (hist_pos + q_frames > hist_len) {
-            const uint32_t n = (uint32_t)(hist_keep * ch);
-            hipLaunchKernelGGL(og_bus_conv_move, dim3((n + 255) / 256), dim3(256), 0, stream, d_hist + (hist_pos - hist_keep) * ch, d_hist, n);
-            hist_pos = hist_keep;
-        }
-        sum_dst = d_hist + hist_pos * ch;
-    }
+    BusConvolver::Launch conv_launch{};
+    if (post_conv) sum_dst = conv_place_dry(conv_launch);
     for (uint32_t c = 0; c < ch; ++c) { // one tree per channel plane; the last pass interleaves Frame<2> samples
         const float* src = d_partials + (size_t)c * A.partial_plane;
         uint32_t rows = n_wg;
@@ -815,43 +820,7 @@ void og_engine::flush_bus()
         hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
     }
     HIPCK(hipGetLastError());
-    if (post_conv) { // one pass per run of blocks queued under the same responses -- as a rule the whole batch
-        const uint32_t fade_len = conv_fade_len();
-        for (size_t b0 = 0, f0 = 0; b0 < queue.size();) {
-            size_t b1 = b0;
-            uint32_t nf = 0;
-            while (b1 < queue.size() && queue[b1].conv == queue[b0].conv) nf += queue[b1++].frames;
-            const ConvCfg& cf = q_conv[queue[b0].conv];
-            const uint64_t t0 = q_frame0 + f0;
-            const int64_t buf_lo = -(int64_t)(hist_pos + f0);
-            auto response = [&](const std::shared_ptr<ConvIR>& ir, uint64_t from, uint32_t frames, float* rows) {
-                OgConvResponse r;
-                r.taps = ir ? ir->d : nullptr;
-                r.n_taps = ir ? ir->K() : 0u;
-                r.n_frames = frames;
-                r.lo = (int32_t)std::max<int64_t>(buf_lo, from >= t0 ? (int64_t)std::min<uint64_t>(from - t0, 0x7fffffffu) : -(int64_t)std::min<uint64_t>(t0 - from, 0x7fffffffu));
-                r.tap_stride = ir ? ir->stride() : 0u;
-                r.rows = rows;
-                return r;
-            };
-            const uint64_t fade_end = cf.fade_start + fade_len;
-            const OgConvResponse rc = response(cf.cur, cf.cur_from, nf, d_conv_rows);
-            const OgConvResponse ro = response(cf.old, cf.old_from, (cf.old && t0 < fade_end) ? (uint32_t)std::min<uint64_t>(nf, fade_end - t0) : 0u,
-                                               d_conv_rows + conv_rows_half);
-            const float* x = d_hist + (hist_pos + f0) * ch;
-            for (const OgConvResponse* r : {&rc, &ro})
-                if (r->n_frames && r->n_taps)
-                    hipLaunchKernelGGL(og_bus_conv, dim3((r->n_frames + OG_CONV_F - 1) / OG_CONV_F, (r->n_taps + OG_CONV_S - 1) / OG_CONV_S, ch),
-                                       dim3(OG_CONV_LANES), 0, stream, x, ch, *r, conv_row_stride);
-            hipLaunchKernelGGL(og_bus_conv_finish, dim3((nf + 255) / 256, ch), dim3(256), 0, stream, rc, ro, ch, conv_row_stride,
-                               (uint32_t)(t0 - cf.fade_start), fade_len, wet_dst + f0 * ch);
-            b0 = b1;
-            f0 += nf;
-        }
-        hist_pos += q_frames;
-        q_conv.clear();
-        HIPCK(hipGetLastError());
-    }
+    if (post_conv) conv_stage(conv_launch, wet_dst);
     size_t off = 0;
     for (const QueuedBlock& qb : queue) {
         if (post_mix) {
@@ -1464,7 +1433,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
         }
         if (cg.bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&e->d_bus_phase, 4));
         if (cg.bus_stage == ogc::BusStage::Convolver) // Convolver::with_ir(..) / ::new(): the empty response
-            e->conv.cur = e->conv_upload(cg.bus_ir ? cg.bus_ir->data() : nullptr, cg.bus_ir ? cg.bus_ir->size() : 0);
+            e->bus_conv.set_current(e->conv_upload(cg.bus_ir ? cg.bus_ir->data() : nullptr, cg.bus_ir ? cg.bus_ir->size() : 0));
         HIPCK(hipMalloc(&e->d_ev_end, (size_t)n_voices * 4));
         HIPCK(hipMalloc(&e->d_ev_cursor, (size_t)n_voices * 4));
         HIPCK(hipMemset(e->d_ev_end, 0, (size_t)n_voices * 4));
@@ -1533,34 +1502,29 @@ int og_set_bus_ir(og_engine* e, const char* ir_name)
         if (!ir) return set_err(OG_E_INVALID, "unknown impulse response '" + resolved + "'; responses are registered with og_register_ir, og_register_ir_asset or og_register_ir_wav");
         HIPCK(hipSetDevice(e->device));
         // an asset response: the playable form is built first -- nothing of the engine has changed if that is refused
-        std::shared_ptr<og_engine::ConvIR> built;
+        std::shared_ptr<ConvIR> built;
         if (ir.asset) built = e->conv_build_asset(resolved, *ir.asset);
         const size_t k = built ? built->K() : ir.taps->size();
-        if (k > e->hist_keep + 1) { // a longer response than the buffers were sized for (not a real-time path)
+        if (e->bus_conv.outgrows(k)) { // a longer response than the buffers were sized for (not a real-time path)
             e->flush_bus();
             HIPCK(hipStreamSynchronize(e->stream));
             e->conv_alloc(k);
         }
         // the new response replaces a swap no block has picked up yet: that one goes before conv_gc (no launch ever read
         // it), an asset's planes are already held by `built` when the gc runs
-        e->conv_pending = built;
+        e->bus_conv.publish(built);
         e->conv_gc();
-        if (!built) e->conv_pending = e->conv_upload(ir.taps->data(), ir.taps->size());
+        if (!built) e->bus_conv.publish(e->conv_upload(ir.taps->data(), ir.taps->size()));
         return OG_OK;
     });
 }
-
-namespace {
-// the response og_set_bus_ir published last: the swap waiting for the next block, else the one the last block ran under
-const og_engine::ConvIR* published_ir(const og_engine* e) { return e->conv_pending ? e->conv_pending.get() : e->conv.cur.get(); }
-} // namespace
 
 int og_bus_ir_info(const og_engine* e, uint32_t* taps, uint32_t* channels)
 {
     return ogabi::guard([&]() -> int {
     if (!e) return set_err(OG_E_INVALID, "null argument");
     if (!e->conv_on()) return set_err(OG_E_INVALID, "og_bus_ir_info: this engine has no post-mix Convolver");
-    const og_engine::ConvIR* ir = published_ir(e);
+    const ConvIR* ir = e->bus_conv.published();
     if (taps) *taps = ir ? ir->K() : 0u;
     if (channels) *channels = ir ? ir->planes : 1u;
     return OG_OK;
@@ -1573,7 +1537,7 @@ int og_read_bus_ir(const og_engine* e, uint32_t channel, float* out, uint32_t ca
     if (!e || !out) return set_err(OG_E_INVALID, "null argument");
     if (!e->conv_on()) return set_err(OG_E_INVALID, "og_read_bus_ir: this engine has no post-mix Convolver");
     if (channel >= e->cg->voice_channels) return set_err(OG_E_INVALID, "og_read_bus_ir: the bus has " + std::to_string(e->cg->voice_channels) + " channels");
-    const og_engine::ConvIR* ir = published_ir(e);
+    const ConvIR* ir = e->bus_conv.published();
     const uint32_t k = ir ? ir->K() : 0u;
     if (capacity < k) return set_err(OG_E_INVALID, "og_read_bus_ir: the output holds " + std::to_string(capacity) + " taps, the response has " + std::to_string(k));
     if (k) memcpy(out, ir->taps.data() + (size_t)(ir->planes > 1 ? channel : 0u) * k, (size_t)k * 4);

@@ -22,6 +22,7 @@
 
 #include "../../include/oscen_gpu.h"
 #include "og_abi.h"
+#include "og_bus_conv_host.h"
 #include "og_graph.h"
 #include "og_jit.h"
 #include "og_node_array_host.h"
@@ -252,38 +253,12 @@ struct og_engine {
     float* d_mono = nullptr;      // summed voices before the post-mix stage
     float* d_bus_phase = nullptr; // Tremolo.phase
     // ---- post-mix Convolver (og_bus_conv.hip.h) ---------------------------------------------------
-    // A response lives on the device from og_set_bus_ir (or og_create) until the engine is destroyed or a later
-    // og_set_bus_ir finds the stream idle: launches already queued may still read it.
-    // planes == 1: one tap plane shared by every bus channel (a mono response, a one-channel asset, any asset on a mono bus);
-    // otherwise one plane per bus channel, K() floats apart, plane-major on the device and in the host copy
-    struct ConvIR {
-        float* d = nullptr;
-        std::vector<float> taps; // host copy (snapshots, og_read_bus_ir): [planes][K]
-        uint32_t planes = 1;
-        uint32_t K() const { return (uint32_t)(taps.size() / planes); }
-        uint32_t stride() const { return planes > 1 ? K() : 0u; } // OgConvResponse::tap_stride
-    };
-    // what a block is rendered under: the current response and, during the crossfade of a swap, the outgoing one; each with
-    // the frame its history is valid from (a new response only sees input from the swap frame on)
-    struct ConvCfg {
-        std::shared_ptr<ConvIR> cur, old;
-        uint64_t cur_from = 0, old_from = 0, fade_start = 0;
-        bool same(const ConvCfg& o) const
-        {
-            return cur == o.cur && old == o.old && cur_from == o.cur_from && old_from == o.old_from && fade_start == o.fade_start;
-        }
-    };
-    ConvCfg conv;                          // the state after the last queued block
-    std::shared_ptr<ConvIR> conv_pending;  // og_set_bus_ir: takes effect at the first frame of the next block
-    std::vector<ConvCfg> q_conv;           // configurations of the queued blocks (QueuedBlock::conv)
-    std::vector<float*> conv_bufs;         // every device tap buffer this engine holds (conv_gc frees the unused ones)
-    // history: interleaved frames, [hist_len][voice_channels]; the next batch's dry bus goes to frame hist_pos and at least
-    // hist_keep frames in front of it hold the input that came before (zeros before the first block)
-    float* d_hist = nullptr;
-    size_t hist_len = 0, hist_keep = 0, hist_pos = 0;
-    float* d_conv_rows = nullptr; // partial rows: [current | outgoing][segment][channel][conv_row_stride]
-    uint32_t conv_row_stride = 0;
-    size_t conv_rows_half = 0;
+    // The host bookkeeping is og_bus_conv_host.h's: which response runs over which frames, where in the history, how large
+    // the buffers are.  The engine owns the device memory and does the device work the class's plans describe.
+    BusConvolver bus_conv;
+    float* d_hist = nullptr;       // history: [bus_conv.hist_len()][voice_channels]
+    float* d_conv_rows = nullptr;  // partial rows: 2 x bus_conv.rows_half() floats
+    std::vector<float*> conv_bufs; // every device tap buffer this engine holds (conv_gc frees the unused ones)
     bool conv_on() const { return cg->bus_stage == ogc::BusStage::Convolver && bus_stage; }
     uint32_t conv_fade_len() const { return (uint32_t)std::max(1.0f, roundf(0.02f * sr)); } // prepare(): CROSSFADE_SECONDS * sr, rounded, >= 1
     std::shared_ptr<ConvIR> conv_upload(const float* taps, size_t n, uint32_t planes = 1) // n taps per plane
@@ -300,31 +275,28 @@ struct og_engine {
     }
     // og_set_bus_ir on an asset response: conformed to the engine's rate and mapped onto the bus's channels on the device
     std::shared_ptr<ConvIR> conv_build_asset(const std::string& name, const ogc::IrAsset& a);
-    void conv_retire(std::shared_ptr<ConvIR>& ir) { ir.reset(); }
     void conv_gc() // free the taps no response in use points at; only with nothing queued and the stream idle
     {
         if (!queue.empty() || hipStreamQuery(stream) != hipSuccess) return;
         std::vector<float*> keep;
         for (float* p : conv_bufs) {
-            bool used = false;
-            for (const ConvIR* ir : {conv.cur.get(), conv.old.get(), conv_pending.get()}) used = used || (ir && ir->d == p);
-            if (used) keep.push_back(p);
+            if (bus_conv.holds(p)) keep.push_back(p);
             else (void)hipFree(p);
         }
         conv_bufs.swap(keep);
     }
-    // (re)size the history and the partial rows for responses of up to need_hist + 1 taps and the current batch size,
-    // keeping the history; the stream is idle (callers launch the queue and wait first)
-    void conv_alloc(size_t need_hist);
+    // (re)size the history and the partial rows for responses of up to k taps and the current launch capacity, keeping
+    // the history; the stream is idle (callers launch the queue and wait first)
+    void conv_alloc(size_t k);
+    void conv_clear_history() { HIPCK(hipMemsetAsync(d_hist, 0, bus_conv.hist_len() * cg->voice_channels * 4, stream)); }
     void conv_reset() // prepare(): cleared history, no fade; the current response stays
     {
         if (!d_hist) return;
-        HIPCK(hipMemsetAsync(d_hist, 0, hist_len * cg->voice_channels * 4, stream));
-        hist_pos = hist_keep;
-        conv_retire(conv.old);
-        conv.cur_from = conv.old_from = conv.fade_start = 0;
-        q_conv.clear();
+        conv_clear_history();
+        bus_conv.reset();
     }
+    float* conv_place_dry(BusConvolver::Launch& l); // plan the launch; where its dry sum goes (flush_bus)
+    void conv_stage(BusConvolver::Launch& l, float* wet); // the post-mix stage of flush_bus
     // ---- SamplePlayer: the device sample pool ------------------------------------------------------------------------
     // og_load_sample appends a sample to the pool once per width the graph's players have (the reference's Vec<F>,
     // frame-major) and gives it the next index; the descriptor table [player][sample_cap]{offset in floats, frames} is what
@@ -435,7 +407,7 @@ struct og_engine {
         float* dst; // where the block's bus goes
         uint32_t frames;
         float trem_rate, trem_depth;
-        uint32_t conv; // index into q_conv (post-mix Convolver)
+        uint32_t conv; // BusConvolver::queue_block (post-mix Convolver)
     };
     std::vector<QueuedBlock> queue;
     uint64_t q_frame0 = 0;   // absolute frame of the first queued block

@@ -38,18 +38,12 @@ constexpr uint32_t SNAP_CONV_MAGIC = 0x56434E4Fu; // "ONCV"
 // stays what it was), the section has another magic and `reserved` holds the planes of the two responses (current | outgoing
 // << 16); the taps of a response are then its planes back to back, k taps each
 constexpr uint32_t SNAP_CONVP_MAGIC = 0x50434E4Fu; // "ONCP"
-uint32_t conv_planes(const std::shared_ptr<og_engine::ConvIR>& ir) { return ir ? ir->planes : 1u; }
-bool conv_per_channel(const og_engine* e) { return conv_planes(e->conv.cur) > 1 || conv_planes(e->conv.old) > 1; }
-size_t conv_hist_frames(const og_engine* e)
-{
-    const uint32_t k = std::max(e->conv.cur ? e->conv.cur->K() : 0u, e->conv.old ? e->conv.old->K() : 0u);
-    return k ? k - 1 : 0;
-}
 size_t conv_bytes(const og_engine* e)
 {
     if (!e->conv_on()) return 0;
-    return sizeof(SnapConv) + ((e->conv.cur ? e->conv.cur->taps.size() : 0u) + (e->conv.old ? e->conv.old->taps.size() : 0u) +
-                               conv_hist_frames(e) * e->cg->voice_channels) * 4;
+    const ConvCfg& cv = e->bus_conv.cfg();
+    return sizeof(SnapConv) + ((cv.cur ? cv.cur->taps.size() : 0u) + (cv.old ? cv.old->taps.size() : 0u) +
+                               e->bus_conv.tail_frames() * e->cg->voice_channels) * 4;
 }
 
 // SamplePlayer: a section of its own at the very end -- the loaded samples' names and shapes in index order (the per-voice
@@ -172,20 +166,21 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
         if (!e->phys_of.empty()) memcpy(p, e->phys_of.data(), (size_t)e->V * sizeof(uint32_t));
         p += e->phys_of.empty() ? 0 : (size_t)e->V * sizeof(uint32_t);
         if (e->conv_on()) {
-            const auto& cv = e->conv;
-            const uint32_t kc = cv.cur ? cv.cur->K() : 0u, ko = cv.old ? cv.old->K() : 0u;
-            const size_t hf = conv_hist_frames(e), vc = e->cg->voice_channels;
-            const bool per_channel = conv_per_channel(e);
-            const size_t nc = (size_t)kc * conv_planes(cv.cur), no = (size_t)ko * conv_planes(cv.old);
+            const ConvCfg& cv = e->bus_conv.cfg();
+            const uint32_t kc = ConvCfg::taps_of(cv.cur), ko = ConvCfg::taps_of(cv.old);
+            const uint32_t pc = ConvCfg::planes_of(cv.cur), po = ConvCfg::planes_of(cv.old);
+            const size_t hf = e->bus_conv.tail_frames(), vc = e->cg->voice_channels;
+            const bool per_channel = cv.per_channel();
+            const size_t nc = (size_t)kc * pc, no = (size_t)ko * po;
             const SnapConv sc{per_channel ? SNAP_CONVP_MAGIC : SNAP_CONV_MAGIC, (uint32_t)vc, kc, cv.old ? ko : 0xFFFFFFFFu, cv.cur_from, cv.old_from, cv.fade_start, (uint32_t)hf,
-                              per_channel ? (conv_planes(cv.cur) | (conv_planes(cv.old) << 16)) : 0u};
+                              per_channel ? (pc | (po << 16)) : 0u};
             memcpy(p, &sc, sizeof sc);
             p += sizeof sc;
             if (nc) memcpy(p, cv.cur->taps.data(), nc * 4);
             p += nc * 4;
             if (no) memcpy(p, cv.old->taps.data(), no * 4);
             p += no * 4;
-            if (hf) e->bounce.d2h(p, e->d_hist + (e->hist_pos - hf) * vc, hf * vc * 4, e->stream); // (hf <= hist_keep <= hist_pos)
+            if (hf) e->bounce.d2h(p, e->d_hist + e->bus_conv.tail_at(hf) * vc, hf * vc * 4, e->stream);
             p += hf * vc * 4;
         }
         if (!e->cg->players.empty()) {
@@ -389,18 +384,14 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             const size_t vc = e->cg->voice_channels;
             const size_t ko = sc.k_old == 0xFFFFFFFFu ? 0u : sc.k_old;
             const float* q = (const float*)((const char*)src + len + sizeof sc);
-            if (sc.hist_frames > e->hist_keep) e->conv_alloc(sc.hist_frames);
+            const size_t kmax = std::max<size_t>(sc.k_cur, ko); // (validated above: hist_frames is its reach)
+            if (e->bus_conv.outgrows(kmax)) e->conv_alloc(kmax);
             const size_t nc = (size_t)sc.k_cur * pl_cur, no = ko * pl_old;
-            e->conv.cur = e->conv_upload(q, sc.k_cur, pl_cur);
-            e->conv.old = sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + nc, ko, pl_old);
-            e->conv.cur_from = sc.cur_from;
-            e->conv.old_from = sc.old_from;
-            e->conv.fade_start = sc.fade_start;
-            e->conv_pending.reset();
-            HIPCK(hipMemsetAsync(e->d_hist, 0, e->hist_len * vc * 4, e->stream));
-            e->hist_pos = e->hist_keep;
+            auto cur = e->conv_upload(q, sc.k_cur, pl_cur);
+            e->bus_conv.restore(cur, sc.k_old == 0xFFFFFFFFu ? nullptr : e->conv_upload(q + nc, ko, pl_old), sc.cur_from, sc.old_from, sc.fade_start);
+            e->conv_clear_history();
             if (sc.hist_frames)
-                e->bounce.h2d(e->d_hist + (e->hist_pos - sc.hist_frames) * vc, q + nc + no, (size_t)sc.hist_frames * vc * 4, e->stream);
+                e->bounce.h2d(e->d_hist + e->bus_conv.tail_at(sc.hist_frames) * vc, q + nc + no, (size_t)sc.hist_frames * vc * 4, e->stream);
             HIPCK(hipStreamSynchronize(e->stream));
             e->conv_gc();
         }

@@ -339,6 +339,61 @@ def test_second_swap_during_a_fade_restarts_from_the_current_response():
     assert np.max(np.abs(c[t2 + FADE:])) > 1e-3
 
 
+def test_swap_to_a_longer_response_keeps_the_outgoing_history():
+    """A (300 taps: the history is sized for 512 frames) -> B (700 taps: 768) before the third block.  The history is
+    reallocated at the publish; A must still see its full pre-swap input for the 960 frames it fades over.  The model and
+    the bounds are those of test_swap_crossfades_as_the_reference_does."""
+    dry = dry_bus()[:, 0]
+    hA, hB = noise_ir(300, 1), noise_ir(700, 2)
+    assert -(-len(hA) // S) * S == 512 and -(-len(hB) // S) * S == 768
+    ts = 2 * BLOCK
+    with registered(A=hA, B=hB):
+        eng = engine(wet_graph("A"))
+        got = [blocks(eng, 2)]
+        eng.set_bus_ir("B")
+        got.append(blocks(eng, TOTAL // BLOCK - 2))
+    got = np.concatenate(got)[:, 0].astype(np.float64)
+    old, old_base = conv64(hA, dry)
+    new, new_base = conv64(hB, dry, since=ts)
+    gn, go = fade_gains(FADE)
+    assert np.max(np.abs(old)) > 1e-3 and np.max(np.abs(new[ts:])) > 1e-3
+    check_rule(got[:ts], old[:ts], old_base[:ts], "before")
+    fade = slice(ts, ts + FADE)
+    ref = new[fade] * gn + old[fade] * go
+    bound = 2e-6 * (old_base[fade] + new_base[fade]) + 1e-6 * (np.abs(new[fade]) + np.abs(old[fade]))
+    err = np.abs(got[fade] - ref)
+    observed.note(float(np.max(err / np.maximum(bound, 1e-30))), "fade")
+    assert np.all(err <= bound), float(np.max(err / np.maximum(bound, 1e-30)))
+    # A's part of the fade comes from input before the swap: without it the error would be far outside the bound
+    lost, _ = conv64(hA, dry, since=ts)
+    assert np.max(np.abs((old[fade] - lost[fade]) * go) - bound) > 1e-3
+    check_rule(got[ts + FADE:], new[ts + FADE:], new_base[ts + FADE:], "after")
+
+
+def test_batching_changed_in_mid_stream():
+    """three blocks at a queue of 1, then set_bus_batching(8) -- the history and the rows are re-sized for the longer
+    launch -- and the remaining blocks in one launch: bit-identical to eight plain blocks"""
+    h = noise_ir(2 * S + 3, 7)
+    with registered(room=h):
+        g = wet_graph("room")
+        want = blocks(engine(g), TOTAL // BLOCK)
+        eng = engine(g)
+        head = blocks(eng, 3)
+        eng.set_bus_batching(8)
+        rest = TOTAL // BLOCK - 3
+        buf = DeviceBuffer(rest * BLOCK * 4)
+        try:
+            for b in range(rest):
+                eng.process_block_async(BLOCK, buf.ptr.value + b * BLOCK * 4)
+            eng.flush()
+            eng.synchronize()
+            tail = buf.to_host().reshape(rest * BLOCK, 1)
+        finally:
+            buf.free()
+    assert float(np.abs(want).max()) > 1e-3
+    assert np.array_equal(np.concatenate([head, tail]), want)
+
+
 def test_empty_convolver_is_silent_until_a_response_is_set():
     dry = dry_bus()[:, 0]
     hB = noise_ir(300, 2)
