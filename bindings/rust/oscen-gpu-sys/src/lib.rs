@@ -45,6 +45,8 @@ extern "C" {
     pub fn og_render(e: *mut og_engine, total_frames: u64, block: u32, out: *mut c_float) -> c_int;
     pub fn og_latency_samples(e: *const og_engine) -> u32;
     pub fn og_post_mix_kind(e: *const og_engine) -> c_int;
+    pub fn og_post_mix_info(e: *const og_engine, n_nodes: *mut u32, in_channels: *mut u32, out_channels: *mut u32, state_words: *mut u32) -> c_int;
+    pub fn og_read_post_mix_input(e: *mut og_engine, out: *mut f32, frames: u32) -> c_int;
     pub fn og_last_error() -> *const c_char;
 }
 

@@ -310,6 +310,21 @@ impl<const IN: usize> GpuGraph<IN> {
         }
         Ok(out)
     }
+    /// the post-mix graph (wrapper-level nodes behind the voice sum): (nodes, channels of the sum, channels of the bus, state words)
+    pub fn post_mix_info(&self) -> Result<(u32, u32, u32, u32), GpuError> {
+        let (mut nodes, mut cin, mut cout, mut words) = (0u32, 0u32, 0u32, 0u32);
+        ck(unsafe { sys::og_post_mix_info(self.e, &mut nodes, &mut cin, &mut cout, &mut words) })?;
+        Ok((nodes, cin, cout, words))
+    }
+    /// the dry voice sum that went into the post-mix graph: the last `frames` frames rendered, interleaved by voice channel
+    pub fn post_mix_input(&mut self, frames: u32) -> Result<Vec<f32>, GpuError> {
+        let (mut cin, mut unused) = (0u32, 0u32);
+        ck(unsafe { sys::og_post_mix_info(self.e, &mut unused, &mut cin, std::ptr::null_mut(), std::ptr::null_mut()) })?;
+        let mut out = vec![0.0f32; (frames as usize * cin as usize).max(1)];
+        ck(unsafe { sys::og_read_post_mix_input(self.e, out.as_mut_ptr(), frames) })?;
+        out.truncate(frames as usize * cin as usize);
+        Ok(out)
+    }
     /// `graph.<node>.<field>` of every voice in `first_voice .. first_voice + n` (the generated struct's node fields are
     /// public in the reference; here a node's persistent fields are planes of the state image): "node.field",
     /// "array[i].field", "nested.node.field"

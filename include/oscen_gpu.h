@@ -185,11 +185,18 @@ int og_unregister_function(const char* name);
 int og_register_graph_type(const char* type_name, const og_graph_desc* g);
 int og_unregister_graph_type(const char* type_name);
 
-/* A node of the poly WRAPPER graph that runs once on the summed voices (e.g.
- * `tremolo = Tremolo::new()` with `voices.output -> tremolo.input; tremolo.output -> out`,
- * examples/electric-piano/src/main.rs:56,88-96).  Wire it with og_graph_connect:
- * "<voice output name>" -> "node.input", value inputs -> "node.rate"/"node.depth",
- * "node.output" -> "<second graph output>" (Frame<2>: the engine then has 2 channels). */
+/* A node of the poly WRAPPER graph that runs once per frame on the summed voices -- a node of the POST-MIX GRAPH.  Any
+ * constructor with a device body or registered with og_register_node (scalar state), any number of such nodes: a master
+ * filter, an echo through og_graph_connect_via, a gain, an LFO that feeds only such nodes, a user limiter.  Wire them with
+ * og_graph_connect: "<voice output name>" -> "node.input" (the voice sum, f32 or Frame<2..4>), broadcast value inputs
+ * (block-uniform or [ramp: N]) and expressions over post-mix nodes -> their ports, post-mix outputs -> the other graph
+ * outputs, which form the engine's bus in declaration order (at most 4 channels; og_channels).  The voice kernel is the one
+ * the graph has without them; they are compiled into a kernel of their own (og_post_mix_info).
+ * A lone `Tremolo::new` (examples/electric-piano/src/main.rs:56,88-96: value inputs -> "node.rate"/"node.depth",
+ * "node.output" -> a Frame<2> output) and a lone Convolver keep their own stages and cannot be combined with other post-mix
+ * nodes.  OG_E_UNSUPPORTED, at og_create / og_graph_kernel_source: an oversampled, sample-playing or array-field node there,
+ * an event edge or a per-voice input into one, a node that feeds both sides, two voice outputs into the post-mix graph, a
+ * post-mix output fed back into the voices. */
 int og_graph_add_bus_node(og_graph_desc* g, const char* name, const char* type_ctor, const float* args,
                           uint32_t n_args);
 /* Impulse responses by name: what `Convolver::with_ir(reverb_ir())` resolves -- the call's path as written or its last
@@ -252,7 +259,8 @@ void og_graph_free(og_graph_desc* g);
  * inspection / ahead-of-time builds).  Returns the length; copies at most cap-1 bytes. */
 int64_t og_graph_kernel_source(const og_graph_desc* g, char* buf, size_t cap);
 /* ... and that of the specialised units generated next to it (see og_kernel_fold_tier): tier 0 is the source above, 1 the zero
- * variant's unit, 2 the deeper zero variant's.  A graph without such a unit has length 0. */
+ * variant's unit, 2 the deeper zero variant's, 3 the post-mix graph's unit (og_kp_<hash>_00 / _10).  A graph without such a
+ * unit has length 0. */
 int64_t og_graph_variant_source(const og_graph_desc* g, int tier, char* buf, size_t cap);
 /* Compile that source with hiprtc for `arch` (e.g. "gfx950") without touching a
  * device -- the path og_create() takes for graphs that were not compiled ahead
@@ -476,6 +484,14 @@ uint32_t og_latency_samples(const og_engine* e); /* emit_struct.rs:534-570 */
  * buses of several engines itself (oscen_amd/distributed.py) may sum AFTER a linear post-mix stage; for kind 2 it must sum
  * the voice sums first and run the node once, as og_cluster_* does. */
 int og_post_mix_kind(const og_engine* e);
+/* The post-mix GRAPH of an engine (kind 2: wrapper-level nodes behind the voice sum, og_graph_add_bus_node): how many nodes it
+ * holds, the channels of the voice sum it reads and of the bus it writes, the words of its state image (one "voice";
+ * og_read_state_field(e, "<node>.<field>", 0, 1, out) reads one).  Any pointer may be null.  OG_E_INVALID without one. */
+int og_post_mix_info(const og_engine* e, uint32_t* n_nodes, uint32_t* in_channels, uint32_t* out_channels, uint32_t* state_words);
+/* The dry voice sum that went into the post-mix graph: the last `frames` frames rendered, out[frames][og_voice_channels()]
+ * (at most the frames of the last launch: the last block, or the last blocks of a queue).  Launches the queue first.
+ * OG_E_INVALID on an engine without a post-mix graph. */
+int og_read_post_mix_input(og_engine* e, float* out, uint32_t frames);
 /* Swap the post-mix Convolver's response for a registered one.  It takes effect at the first frame of the next block
  * handed to the engine (it travels with the queued block: correct under og_set_bus_batching) with Convolver::process's
  * crossfade (convolution/mod.rs:535-573): the new response starts on empty history, the old one keeps running for

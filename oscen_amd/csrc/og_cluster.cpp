@@ -485,6 +485,9 @@ int og_cluster_create(const og_graph_desc* g, uint64_t n_voices_total, const int
             std::unique_ptr<og_engine> e(raw); // (owned here until the cluster has it: alloc_bus_buffers may throw)
             if (e->cg->bus_stage == ogc::BusStage::Convolver) // (the stage would run once on the root, after the reduce: not built)
                 throw ogabi::Unsupported("a cluster over a graph with a post-mix Convolver is not supported in this version (the convolver runs on one device's bus)");
+            if (e->cg->post) // (its kernel would run once on the root, on the reduced sum: not built)
+                throw ogabi::Unsupported("a cluster over a graph with a post-mix graph (nodes '" + e->cg->post->post_nodes.front() +
+                                         "' ...) is not supported in this version (the post-mix kernel runs on one device's bus)");
             e->bus_stage = false; // shards hand over the voice sum; the post-mix node runs once, on the root
             {
                 HIPCK(hipSetDevice(e->device));

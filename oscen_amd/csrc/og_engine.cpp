@@ -408,6 +408,10 @@ og_engine::~og_engine()
     for (int k = 0; k < OG_MAX_RINGS; ++k) (void)hipFree(d_ring[k]);
     (void)hipFree(d_mono);
     (void)hipFree(d_bus_phase);
+    (void)hipFree(d_pm_state);
+    for (int k = 0; k < OG_MAX_RINGS; ++k) (void)hipFree(d_pm_ring[k]);
+    (void)hipFree(d_pm_in);
+    (void)hipFree(d_pm_ev);
     (void)hipFree(d_hist);
     (void)hipFree(d_conv_rows);
     for (float* p : conv_bufs) (void)hipFree(p);
@@ -488,7 +492,31 @@ void og_engine::upload_initial_state()
         HIPCK(hipMemsetAsync(d_ring[k], 0, (size_t)cap * V * 4, stream));
     }
     narr_fill(); // every array field of a registered node type holds its `init`
+    pm_reset();
     HIPCK(hipStreamSynchronize(stream));
+}
+
+// the post-mix graph's state image: one voice
+void og_engine::pm_reset()
+{
+    if (!post_on()) return;
+    const ogc::CompiledGraph& p = *cg->post;
+    const ogc::UEnv e = pm_env();
+    std::vector<uint32_t> img(p.state.size());
+    for (size_t w = 0; w < img.size(); ++w) img[w] = p.state[w].init(e);
+    if (!img.empty()) HIPCK(hipMemcpyAsync(d_pm_state, img.data(), img.size() * 4, hipMemcpyHostToDevice, stream));
+    for (size_t k = 0; k < p.rings.size(); ++k) {
+        const uint32_t cap = p.rings[k].capacity(sr);
+        if (cap != pm_ring_cap[k]) {
+            if (d_pm_ring[k]) HIPCK(hipFree(d_pm_ring[k]));
+            d_pm_ring[k] = nullptr;
+            pm_ring_cap[k] = 0;
+            HIPCK(hipMalloc(&d_pm_ring[k], (size_t)cap * 4));
+            pm_ring_cap[k] = cap;
+        }
+        HIPCK(hipMemsetAsync(d_pm_ring[k], 0, (size_t)cap * 4, stream));
+    }
+    HIPCK(hipStreamSynchronize(stream)); // (the image dies here)
 }
 
 // ---- event timeline: the device halves of og_timeline.h's two update paths ---------------------------------------------
@@ -573,7 +601,7 @@ bool og_engine::rcp_cover(uint32_t need)
 void og_engine::alloc_bus_buffers(uint32_t batch)
 {
     HIPCK(hipStreamSynchronize(stream));
-    for (float** p : {&d_partials, &d_partials2, &d_mono, &d_stage_bus})
+    for (float** p : {&d_partials, &d_partials2, &d_mono, &d_stage_bus, &d_pm_in})
         if (*p) {
             HIPCK(hipFree(*p));
             *p = nullptr;
@@ -587,6 +615,11 @@ void og_engine::alloc_bus_buffers(uint32_t batch)
     HIPCK(hipMalloc(&d_stage_bus, max_frames * OG_MAX_BUS_CHANNELS * 4));
     if (cg->bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&d_mono, max_frames * 4));
     if (cg->bus_stage == ogc::BusStage::Convolver) conv_alloc(bus_conv.longest_taps());
+    if (post_on()) { // the rows the last reduce pass writes and the post-mix kernel reads in whole 16-frame chunks (cap_frames is a multiple)
+        HIPCK(hipMalloc(&d_pm_in, max_frames * vc * 4));
+        HIPCK(hipMemset(d_pm_in, 0, max_frames * vc * 4));
+        pm_last_frames = 0;
+    }
     const size_t rows = (size_t)(cg->n_ramps + cg->n_streams);
     for (int i = 0; i < RAMP_RING && rows; ++i) {
         if (d_ramp[i]) HIPCK(hipFree(d_ramp[i]));
@@ -797,9 +830,11 @@ void og_engine::flush_bus()
     const bool post_mix = cg->bus_stage == ogc::BusStage::Tremolo && bus_stage;
     const bool post_conv = conv_on();
     const uint32_t ch = cg->voice_channels; // summed voices: mono, or Frame<2> voices (a post-mix node writes its Frame<2> bus itself)
+    const bool post_graph = post_on(); // the post-mix kernel writes the bus (cg->channels wide) where the last reduce pass would have
+    const uint32_t och = post_graph ? cg->channels : ch;
     bool contiguous = !post_mix;
     for (size_t k = 1; k < queue.size() && contiguous; ++k)
-        contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * ch;
+        contiguous = queue[k].dst == queue[k - 1].dst + (size_t)queue[k - 1].frames * och;
     float* sum_dst = post_mix ? d_mono : (contiguous ? queue[0].dst : d_stage_bus);
     float* const wet_dst = sum_dst;
     BusConvolver::Launch conv_launch{};
@@ -817,9 +852,41 @@ void og_engine::flush_bus()
             rows = groups;
             tmp = tmp + (size_t)groups * n_chunks16 * OG_RED_FRAMES; // next level writes behind this one
         }
-        hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
+        if (post_graph) // planar, straight into the rows the post-mix kernel reads
+            hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, d_pm_in + (size_t)c * cap_frames, 1u, 0u);
+        else
+            hipLaunchKernelGGL(og_bus_reduce, dim3(n_chunks16, 1), dim3(1024), 0, stream, src, rows, q_frames, sum_dst, ch, c);
     }
     HIPCK(hipGetLastError());
+    if (post_graph) { // the nodes behind the sum: one wave over all q_frames of the launch, into the destination
+        const ogc::CompiledGraph& p = *cg->post;
+        OgBlockArgs P;
+        memset(&P, 0, sizeof P);
+        P.n_voices = 1;
+        P.frames = q_frames;
+        P.ramp_stride = (uint32_t)cap_frames;
+        P.lanes = OG_WAVE;
+        P.frame0 = q_frame0;
+        P.state = d_pm_state;
+        P.ev_cursor = d_pm_ev;
+        P.ev_end = d_pm_ev + 1;
+        P.ramp_table = A.ramp_table; // (the post-mix graph declares the wrapper's broadcast inputs in order: the same ramp rows)
+        for (size_t k = 0; k < p.rings.size(); ++k) {
+            P.rings[k] = d_pm_ring[k];
+            P.ring_cap[k] = pm_ring_cap[k];
+        }
+        const ogc::UEnv pe = pm_env();
+        for (const auto& up : p.uprogs) P.slots[up.dst] = up.fn(pe);
+        uint32_t* io = P.slots + p.pm_slot0;
+        io[0] = (uint32_t)((uintptr_t)d_pm_in & 0xFFFFFFFFu);
+        io[1] = (uint32_t)((uint64_t)(uintptr_t)d_pm_in >> 32);
+        io[2] = (uint32_t)((uintptr_t)wet_dst & 0xFFFFFFFFu);
+        io[3] = (uint32_t)((uint64_t)(uintptr_t)wet_dst >> 32);
+        io[4] = (uint32_t)cap_frames;
+        pm_jit->launch(P, ramps_on && p.n_ramps > 0, false, stream);
+        pm_last_frames = q_frames;
+        HIPCK(hipGetLastError());
+    }
     if (post_conv) conv_stage(conv_launch, wet_dst);
     size_t off = 0;
     for (const QueuedBlock& qb : queue) {
@@ -827,7 +894,7 @@ void og_engine::flush_bus()
             hipLaunchKernelGGL(og_bus_tremolo, dim3(1), dim3(512), 0, stream, d_mono + off, qb.frames, qb.trem_rate, qb.trem_depth, sr,
                                d_bus_phase, qb.dst);
         } else if (!contiguous) {
-            HIPCK(hipMemcpyAsync(qb.dst, d_stage_bus + off * ch, (size_t)qb.frames * ch * 4, hipMemcpyDeviceToDevice, stream));
+            HIPCK(hipMemcpyAsync(qb.dst, d_stage_bus + off * och, (size_t)qb.frames * och * 4, hipMemcpyDeviceToDevice, stream));
         }
         off += qb.frames;
     }
@@ -1259,11 +1326,12 @@ int64_t og_graph_kernel_source(const og_graph_desc* g, char* buf, size_t cap)
 
 int64_t og_graph_variant_source(const og_graph_desc* g, int tier, char* buf, size_t cap)
 {
-    if (!g || tier < 0 || tier > 2) return set_err(OG_E_INVALID, "null graph or no such tier");
+    if (!g || tier < 0 || tier > 3) return set_err(OG_E_INVALID, "null graph or no such tier");
     int64_t len = -1;
     int rc = guard([&] {
         auto cg = ogc::compile(g->g);
-        const std::string& src = tier == 2 ? cg->zero2_source : (tier == 1 ? cg->zero_source : cg->source);
+        static const std::string none;
+        const std::string& src = tier == 3 ? (cg->post ? cg->post->source : none) : (tier == 2 ? cg->zero2_source : (tier == 1 ? cg->zero_source : cg->source));
         len = (int64_t)src.size();
         if (buf && cap) {
             size_t n = std::min(cap - 1, src.size());
@@ -1282,6 +1350,7 @@ int64_t og_graph_jit_check(const og_graph_desc* g, const char* arch)
     int rc = guard([&] {
         auto cg = ogc::compile(g->g);
         len = (int64_t)og_jit_compile_only(*cg, arch);
+        if (cg->post) len += (int64_t)og_jit_compile_only(*cg->post, arch);
         return OG_OK;
     });
     return rc == OG_OK ? len : rc;
@@ -1304,6 +1373,7 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
         if (e->launch && !e->cg->zero_slots.empty()) e->launch_zero = og_find_zero_kernel(e->cg->hash);
         if (e->launch && !e->cg->zero2_slots.empty()) e->launch_zero2 = og_find_zero_kernel(e->cg->hash, 2);
         if (!e->launch) e->jit = og_jit_compile(*e->cg); // throws if hiprtc is unavailable or fails
+        if (e->cg->post) e->pm_jit = og_jit_compile(*e->cg->post); // (no built-in graph has a post-mix graph: always compiled here)
         e->V = n_voices;
         // voices per wave: narrow the wave until every SIMD holds two (og_kernel_rt.hip.h)
         {
@@ -1432,6 +1502,11 @@ int og_create(const og_graph_desc* g, uint32_t n_voices, int device_id, og_engin
             }
         }
         if (cg.bus_stage == ogc::BusStage::Tremolo) HIPCK(hipMalloc(&e->d_bus_phase, 4));
+        if (cg.post) {
+            HIPCK(hipMalloc(&e->d_pm_state, std::max<size_t>(1, cg.post->state.size()) * 4));
+            HIPCK(hipMalloc(&e->d_pm_ev, 2 * 4));
+            HIPCK(hipMemset(e->d_pm_ev, 0, 2 * 4));
+        }
         if (cg.bus_stage == ogc::BusStage::Convolver) // Convolver::with_ir(..) / ::new(): the empty response
             e->bus_conv.set_current(e->conv_upload(cg.bus_ir ? cg.bus_ir->data() : nullptr, cg.bus_ir ? cg.bus_ir->size() : 0));
         HIPCK(hipMalloc(&e->d_ev_end, (size_t)n_voices * 4));
@@ -2141,6 +2216,9 @@ static int find_state_word(const og_engine* e, const char* path)
         if (p[k] == '.' && k != last) p[k] = '_';
     for (size_t w = 0; w < e->cg->state.size(); ++w)
         if (e->cg->state[w].name == p) return (int)w;
+    // the fields of the post-mix nodes: the words of the second state image, numbered behind the voices'
+    for (size_t w = 0; e->cg->post && w < e->cg->post->state.size(); ++w)
+        if (e->cg->post->state[w].name == p) return (int)(e->cg->state.size() + w);
     return -1;
 }
 
@@ -2155,11 +2233,16 @@ int og_read_state_field(og_engine* e, const char* path, uint32_t first_voice, ui
     if (!e || !path || (n && !out)) return set_err(OG_E_INVALID, "null argument");
     const int w = find_state_word(e, path);
     if (w < 0) return set_err(OG_E_INVALID, std::string("no state field '") + path + "'");
+    const bool post_field = (size_t)w >= e->cg->state.size();
+    if (post_field && (first_voice != 0 || n != 1))
+        return set_err(OG_E_INVALID, std::string("state field '") + path + "' belongs to a post-mix node: there is one of it (first_voice 0, n 1)");
     if ((uint64_t)first_voice + n > e->V) return set_err(OG_E_INVALID, "voice range out of bounds");
     return guard([&] {
         HIPCK(hipSetDevice(e->device));
         e->flush_bus();
-        if (n && e->phys_of.empty()) {
+        if (post_field) {
+            e->bounce.d2h(out, e->d_pm_state + ((size_t)w - e->cg->state.size()), 4, e->stream);
+        } else if (n && e->phys_of.empty()) {
             e->bounce.d2h(out, e->d_state + (size_t)w * e->V + first_voice, (size_t)n * 4, e->stream);
         } else if (n) { // grouped voices: gather
             std::vector<uint32_t> plane(e->V);
@@ -2283,7 +2366,42 @@ uint32_t og_num_voices(const og_engine* e) { return e ? e->V : 0; }
 uint32_t og_latency_samples(const og_engine* e) { return e ? e->cg->latency_samples : 0; }
 // (Tremolo and Convolver are the post-mix node types the compiler takes -- og_graph.cpp, bus nodes -- and both are linear in
 // their input)
-int og_post_mix_kind(const og_engine* e) { return (e && e->cg->bus_stage != ogc::BusStage::None) ? 1 : 0; }
+int og_post_mix_kind(const og_engine* e) { return !e ? 0 : (e->cg->post ? 2 : (e->cg->bus_stage != ogc::BusStage::None ? 1 : 0)); }
+
+int og_post_mix_info(const og_engine* e, uint32_t* n_nodes, uint32_t* in_channels, uint32_t* out_channels, uint32_t* state_words)
+{
+    if (!e) return set_err(OG_E_INVALID, "null engine");
+    return guard([&] {
+        if (!e->cg->post) throw ogabi::Error(OG_E_INVALID, "og_post_mix_info: this engine has no post-mix graph");
+        const ogc::CompiledGraph& p = *e->cg->post;
+        if (n_nodes) *n_nodes = (uint32_t)p.post_nodes.size();
+        if (in_channels) *in_channels = e->cg->voice_channels;
+        if (out_channels) *out_channels = e->cg->channels;
+        if (state_words) *state_words = (uint32_t)p.state.size();
+        return OG_OK;
+    });
+}
+
+int og_read_post_mix_input(og_engine* e, float* out, uint32_t frames)
+{
+    if (!e || (frames && !out)) return set_err(OG_E_INVALID, "null argument");
+    return guard([&] {
+        if (!e->cg->post) throw ogabi::Error(OG_E_INVALID, "og_read_post_mix_input: this engine has no post-mix graph");
+        HIPCK(hipSetDevice(e->device));
+        e->flush_bus();
+        if (frames > e->pm_last_frames)
+            throw ogabi::Error(OG_E_INVALID, "og_read_post_mix_input: " + std::to_string(frames) + " frames asked for, the last launch rendered " +
+                                                 std::to_string(e->pm_last_frames));
+        const uint32_t vc = e->cg->voice_channels, first = e->pm_last_frames - frames;
+        std::vector<float> row(frames);
+        for (uint32_t c = 0; c < vc && frames; ++c) { // planar rows -> interleaved frames
+            e->bounce.d2h(row.data(), e->d_pm_in + (size_t)c * e->cap_frames + first, (size_t)frames * 4, e->stream);
+            for (uint32_t f = 0; f < frames; ++f) out[(size_t)f * vc + c] = row[f];
+        }
+        HIPCK(hipStreamSynchronize(e->stream));
+        return OG_OK;
+    });
+}
 uint64_t og_frames_processed(const og_engine* e) { return e ? e->frame_now : 0; }
 uint32_t og_state_words_per_voice(const og_engine* e)
 {

@@ -252,6 +252,34 @@ struct og_engine {
     uint32_t ring_cap[OG_MAX_RINGS] = {0, 0, 0, 0};
     float* d_mono = nullptr;      // summed voices before the post-mix stage
     float* d_bus_phase = nullptr; // Tremolo.phase
+    // ---- post-mix graph (cg->post; og_post_mix.hip.h) -------------------------------------------------
+    // A second state image of ONE voice -- state words, Delay rings [capacity][1] -- and the rows og_bus_reduce writes the
+    // voice sum into ([voice_channels][cap_frames], planar).  flush_bus: voice kernel -> reduce (into d_pm_in) -> post-mix
+    // kernel (into the destination) -> copies.
+    std::unique_ptr<OgJitKernel> pm_jit;
+    uint32_t* d_pm_state = nullptr;
+    float* d_pm_ring[OG_MAX_RINGS] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t pm_ring_cap[OG_MAX_RINGS] = {0, 0, 0, 0};
+    float* d_pm_in = nullptr;
+    uint32_t pm_last_frames = 0; // frames of the last launch: what d_pm_in holds (og_read_post_mix_input)
+    uint32_t* d_pm_ev = nullptr; // {cursor, end} of the post-mix voice: both 0, no event ever reaches it
+    std::vector<float> pm_values; // the post-mix graph's inputs: mirrors of `values` (filled per launch)
+    bool post_on() const { return cg->post != nullptr; }
+    void pm_reset(); // og_init: initial state words (the sample-rate-dependent ones recomputed), fresh zeroed rings
+    size_t pm_ring_words() const
+    {
+        size_t n = 0;
+        for (size_t k = 0; post_on() && k < cg->post->rings.size(); ++k) n += pm_ring_cap[k];
+        return n;
+    }
+    ogc::UEnv pm_env()
+    {
+        const ogc::CompiledGraph& p = *cg->post;
+        pm_values.assign(p.inputs.size(), 0.0f);
+        for (size_t i = 0; i < p.inputs.size(); ++i)
+            if (p.post_input_of[i] >= 0) pm_values[i] = values[(size_t)p.post_input_of[i]];
+        return ogc::UEnv{sr, pm_values.data()};
+    }
     // ---- post-mix Convolver (og_bus_conv.hip.h) ---------------------------------------------------
     // The host bookkeeping is og_bus_conv_host.h's: which response runs over which frames, where in the history, how large
     // the buffers are.  The engine owns the device memory and does the device work the class's plans describe.

@@ -2812,6 +2812,37 @@ GraphDesc lower_poly_wrapper(const GraphDesc& g, PolyInfo* info)
     std::set<std::string> post;
     for (const GEdge& e : g.edges)
         if (root(e.src) == voices && !port(e.dst).empty() && !control.count(root(e.dst)) && root(e.dst) != voices) post.insert(root(e.dst));
+    // ... and the post-mix GRAPH around it: every wrapper-level node downstream of such a node, then every node that feeds
+    // only post-mix nodes (`lfo.output * 800.0 + 1200.0 -> master.cutoff`).  A node that also feeds the voices stays with
+    // them; compile() refuses its edge into the post-mix graph.
+    if (!post.empty()) {
+        auto mentions = [](const std::string& text, const std::string& name) { // `name` as a whole identifier that starts a path
+            for (size_t p = text.find(name); p != std::string::npos; p = text.find(name, p + 1)) {
+                const bool left = p == 0 || !(isalnum((unsigned char)text[p - 1]) || text[p - 1] == '_' || text[p - 1] == '.');
+                const size_t e = p + name.size();
+                if (left && (e == text.size() || !(isalnum((unsigned char)text[e]) || text[e] == '_'))) return true;
+            }
+            return false;
+        };
+        auto wrapper_level = [&](const std::string& n) { return !control.count(n) && n != voices; };
+        for (bool grown = true; grown;) {
+            grown = false;
+            for (const GNode& n : g.nodes) {
+                if (!wrapper_level(n.name) || post.count(n.name)) continue;
+                bool fed_by_post = false, feeds_post = false, feeds_other = false;
+                for (const GEdge& e : g.edges) {
+                    const std::string dr = root(e.dst);
+                    if (dr == n.name && !port(e.dst).empty())
+                        for (const std::string& p : post) fed_by_post = fed_by_post || mentions(e.src, p);
+                    if (mentions(e.src, n.name) && !port(e.dst).empty()) (post.count(dr) ? feeds_post : feeds_other) = true;
+                }
+                if (fed_by_post || (feeds_post && !feeds_other)) {
+                    post.insert(n.name);
+                    grown = true;
+                }
+            }
+        }
+    }
     // outputs: the wrapper's stream outputs; event outputs fed by the MIDI nodes stay on the host
     std::string sum_output; // graph output that carries the summed voices into the post-mix node
     std::set<std::string> dropped;
@@ -2827,7 +2858,12 @@ GraphDesc lower_poly_wrapper(const GraphDesc& g, PolyInfo* info)
     if (!post.empty()) {
         std::string vout;
         for (const GEdge& e : g.edges)
-            if (root(e.src) == voices && post.count(root(e.dst))) vout = port(e.src);
+            if (root(e.src) == voices && post.count(root(e.dst))) {
+                if (!vout.empty() && vout != port(e.src))
+                    fail_unsupported("poly wrapper: more than one voice output feeds the post-mix graph ('" + voices + "." + vout + "' and '" + voices + "." +
+                                     port(e.src) + "' into node '" + root(e.dst) + "'): it takes one voice output, f32 or Frame<2..4>");
+                vout = port(e.src);
+            }
         sum_output = vout;
         for (const GOutput& out : g.outputs)
             if (out.name == sum_output) sum_output = "__voice_sum";
@@ -4374,6 +4410,7 @@ struct BodyWriter {
     std::string rs_sum(const std::vector<int>& st);
     std::string fc_sync(const std::vector<int>& st, const std::string& ind);
     void write_ordinary_kernel();
+    void write_post_kernel();
     void pipeline_lds(const std::vector<std::vector<int>>& groups);
     void write_pipeline_kernel(const std::vector<std::vector<int>>& groups, int tag);
 };
@@ -4635,6 +4672,60 @@ void BodyWriter::write_ordinary_kernel()
     body << "    og::bus_flush(A, c, bus);\n"
          << cat(all_stages, &Codegen::Sect::pre_store) << "    if (c.valid) {\n"
          << cat(all_stages, &Codegen::Sect::store) << vin_store();
+    body << "    }\n    og::voice_end(A, c);\n}\n";
+}
+
+// ---- post-mix kernel: one wave, lane 0 = the one "voice" whose stream input is the voice sum (og_post_mix.hip.h) -----------
+// The same sections as the ordinary kernel -- state in registers for the launch, a tick lambda of the nodes in order, Delay
+// lines staged per chunk -- in a frame built for a serial recurrence: a chunk's input frames are in registers before its
+// first tick (pm_in[], fetched a chunk ahead with 16-byte loads; ST(row) of the unit picks from them), its output frames
+// are collected and stored interleaved with 16-byte stores straight into the destination, nothing goes through the mix-bus
+// tile or partial rows.  No events reach this graph: every full chunk is the straight-line body.
+void BodyWriter::write_post_kernel()
+{
+    const std::string W = std::to_string(out.voice_channels), C = std::to_string(std::max(1, out.n_streams));
+    const std::string OT = out.voice_channels > 1 ? "og::OutN<" + W + ">" : std::string("float");
+    body << "template <bool RAMPS>\n"
+         << "__device__ __forceinline__ void post_block(const OgBlockArgs& A)\n{\n"
+         << "    constexpr bool TAPS = false;\n    (void)TAPS;\n"
+         << (out.rings.empty() ? std::string()
+                               : "    __shared__ float ring_lds[" + std::to_string(out.rings.size()) +
+                                     "][OG_BUS_CHUNK][OG_WAVE];\n    uint32_t cbase = 0;\n")
+         << "    og::VoiceCtx c;\n"
+         << "    og::voice_begin<false, LPV>(A, c);\n"
+         << "    const og::PostIo io = og::post_io(A, " << out.pm_slot0 << ");\n"
+         << "    float pm_in[" << C << "][OG_BUS_CHUNK];\n"
+         << "    uint32_t pbase = 0;\n"
+         << cg.common_decl.str() << cat(all_stages, &Codegen::Sect::decl) << "    if (c.valid) {\n"
+         << cg.common_load.str() << cat(all_stages, &Codegen::Sect::load) << "    }\n";
+    body << "    auto derive = [&]() __attribute__((always_inline)) {\n" << cat(all_stages, &Codegen::Sect::derive) << "    };\n";
+    body << cat(all_stages, &Codegen::Sect::pre) << "    derive();\n";
+    body << "    og::post_fetch(pm_in, io, 0u); // the first chunk's frames; every later chunk's are asked for a chunk ahead\n";
+    if (!out.rings.empty()) body << "    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)\n";
+    body << "    auto tick = [&](const uint32_t f, auto chk) __attribute__((always_inline)) -> " << OT << " {\n" << group_tick({all_stages}, 0);
+    if (cg.frame_end.str().empty()) {
+        body << "        return " << bus_expr << ";\n    };\n";
+    } else {
+        body << "        const auto g_bus = " << bus_expr << ";\n" << cg.frame_log.str() << cg.frame_end.str() << "        return g_bus;\n    };\n";
+    }
+    body << "    for (uint32_t base = 0; base < A.frames; base += OG_BUS_CHUNK) {\n"
+         << "        const uint32_t n = min((uint32_t)OG_BUS_CHUNK, A.frames - base);\n"
+         << "        pbase = base;\n"
+         << (out.rings.empty() ? std::string() : std::string("        cbase = base;\n")) << cat(all_stages, &Codegen::Sect::chunk_begin)
+         << fc_sync(all_stages, "        ")
+         << "        if (n == OG_BUS_CHUNK) {\n"
+         << "            float pm_next[" << C << "][OG_BUS_CHUNK];\n"
+         << "            og::post_fetch_ahead(pm_next, io, base + OG_BUS_CHUNK, A.frames);\n"
+         << "            " << OT << " pm_out[OG_BUS_CHUNK];\n"
+         << "#pragma unroll\n"
+         << "            for (uint32_t j = 0; j < OG_BUS_CHUNK; ++j) pm_out[j] = tick(base + j, og::BoolC<true, true, true>{});\n"
+         << "            og::post_store(io, c, base, pm_out);\n"
+         << "            og::post_take(pm_in, pm_next);\n"
+         << "        } else { // a launch's last, partial chunk: frame by frame, the input read where it lies\n"
+         << "            for (uint32_t j = 0; j < n; ++j) og::post_store1(io, c, base + j, tick(base + j, og::BoolC<true>{}));\n"
+         << "        }\n"
+         << "    }\n";
+    body << cat(all_stages, &Codegen::Sect::pre_store) << "    if (c.valid) {\n" << cat(all_stages, &Codegen::Sect::store) << vin_store();
     body << "    }\n    og::voice_end(A, c);\n}\n";
 }
 
@@ -5228,9 +5319,10 @@ struct Lowered {
 //   form_graph_output         out_edges, out_reads, ev_out_edges, the bus ends  -> bus_expr, out.output_channels / event_outputs / channels
 //   choose_unroll             order, out.rings / players / lpv                  -> unroll, out.valu_estimate
 //   BodyWriter                cg.sec[], cg.xvals, the groups, bus_expr, unroll  -> body
-std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_nodes, bool stage_spec = false)
+// (rules_checked: an expanded description cut out of one that was checked as written -- the voices of a post-mix graph)
+std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_nodes, bool stage_spec = false, bool rules_checked = false)
 {
-    check_reference_rules(g_in);
+    if (!rules_checked) check_reference_rules(g_in);
     auto gen = std::make_unique<Lowered>(g_in);
     gen->out->name = gen->g.name;
     Codegen& cg = gen->cg;
@@ -5261,11 +5353,11 @@ std::unique_ptr<Lowered> lower(const GraphDesc& g_in, const std::set<int>* zero_
 // A zero variant's pass: the kernel body with `nodes` folded, or "" where the graph does not get that variant.  The engine
 // fills the slots and the state of every kernel from the general pass's layout: a variant pass that does not keep it (or does
 // not compile) leaves the graph without the variant -- it never costs the graph its general kernel.
-std::string lower_variant(const GraphDesc& g_in, const std::set<int>& nodes, const CompiledGraph& out, bool stage_spec = false)
+std::string lower_variant(const GraphDesc& g_in, const std::set<int>& nodes, const CompiledGraph& out, bool stage_spec = false, bool rules_checked = false)
 {
     if (nodes.empty()) return std::string();
     try {
-        const auto zgen = lower(g_in, &nodes, stage_spec);
+        const auto zgen = lower(g_in, &nodes, stage_spec, rules_checked);
         const CompiledGraph& z = *zgen->out;
         bool same = z.n_slots == out.n_slots && z.state.size() == out.state.size() && z.n_ramps == out.n_ramps && z.n_streams == out.n_streams &&
                     z.lpv == out.lpv && z.max_pipeline == out.max_pipeline && z.wide4 == out.wide4;
@@ -5668,14 +5760,166 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
 
 } // namespace
 
-// The general pass first; the `_z` pass before the `_z2` set is computed (find_zero_folds reads out.zero_slots); the `_z2`
-// pass folds both sets.
+// ---- post-mix graphs: the partition ------------------------------------------------------------------------------------------
+// A lowered wrapper (or a builder description) marks the wrapper-level nodes behind the voice sum `bus`.  One Tremolo or one
+// Convolver alone is the legacy stage of declare_nodes(); any other set is cut out here into a description of its own.
+bool split_post_mix(const GraphDesc& g, PostSplit& ps)
+{
+    std::set<std::string> bus;
+    const GNode* legacy = nullptr;
+    auto is_legacy = [](const GNode& n) {
+        const NodeTypeInfo* nti = lookup_type(n.type);
+        return n.type == "Tremolo::new" || (nti && !nti->user && normalize_type(n.type).rfind("Convolver", 0) == 0);
+    };
+    for (const GNode& n : g.nodes)
+        if (n.bus) {
+            bus.insert(n.name);
+            if (is_legacy(n)) legacy = &n;
+        }
+    if (bus.empty() || (bus.size() == 1 && legacy)) return false;
+    if (legacy)
+        fail_unsupported("node '" + legacy->name + "': a " + legacy->type.substr(0, legacy->type.find(':')) +
+                         " runs as the only one post-mix (bus) node of a graph in this version -- it cannot be combined with other post-mix nodes");
+    for (const GNode& n : g.nodes) {
+        if (!n.bus) continue;
+        const NodeTypeInfo* nti = lookup_type(n.type);
+        if (!nti) fail("unknown node type '" + n.type + "' (node '" + n.name + "'); custom nodes are added with og_register_node");
+        if (n.rate_factor != 1) fail_unsupported("post-mix node '" + n.name + "': an oversampled (* " + std::to_string(n.rate_factor) + ") node is not supported in a post-mix graph");
+        if (n.type.rfind("SamplePlayer", 0) == 0) fail_unsupported("post-mix node '" + n.name + "': a SamplePlayer is not supported in a post-mix graph");
+        if (nti->lpv > 1 || (nti->user && !nti->user->arrays.empty()))
+            fail_unsupported("post-mix node '" + n.name + "': a node type with array fields (" + n.type + ") is not supported in a post-mix graph");
+        if (!nti->emit) fail_unsupported("post-mix node '" + n.name + "': node type '" + n.type + "' has no device body");
+    }
+    auto trimmed = [](const std::string& s) { return strip_ws(s); };
+    auto dst_node = [&](const GEdge& e) {
+        const std::string d = trimmed(e.dst);
+        const size_t dot = d.find('.');
+        return dot == std::string::npos ? std::string() : d.substr(0, dot);
+    };
+    std::set<std::string> outputs;
+    for (const GOutput& o : g.outputs) outputs.insert(o.name);
+    // the voice sum: the graph output(s) that post-mix nodes read
+    std::set<std::string> sums;
+    for (const GEdge& e : g.edges) {
+        if (!bus.count(dst_node(e))) continue;
+        for (const GOutput& o : g.outputs)
+            if (count_node_refs(e.src, o.name)) sums.insert(o.name);
+    }
+    if (sums.empty()) fail("post-mix (bus) nodes without the voice sum: no post-mix node reads the voice graph's output");
+    if (sums.size() > 1)
+        fail_unsupported("more than one voice output feeds the post-mix graph ('" + *sums.begin() + "' and '" + *std::next(sums.begin()) +
+                         "'): it takes one voice output, f32 or Frame<2..4>");
+    const std::string S = *sums.begin();
+    std::string sum_src; // what the voices put into the sum
+    for (const GEdge& e : g.edges)
+        if (trimmed(e.dst) == S) sum_src = sum_src.empty() ? trimmed(e.src) : sum_src + " + " + trimmed(e.src);
+    std::map<std::string, const GInput*> inputs;
+    for (const GInput& in : g.inputs) inputs[in.name] = &in;
+    ps.voice = GraphDesc();
+    ps.post = GraphDesc();
+    ps.sum_input = S;
+    ps.voice.name = g.name;
+    ps.post.name = g.name + "__post_mix";
+    ps.voice.inputs = g.inputs;
+    for (const GInput& in : g.inputs)
+        if (in.kind == Kind::Value && !in.per_voice) ps.post.inputs.push_back(in);
+    {
+        GInput s;
+        s.name = S;
+        s.kind = Kind::Stream;
+        ps.post.inputs.push_back(s);
+    }
+    for (const GOutput& o : g.outputs) {
+        if (o.name == S) {
+            ps.voice.outputs.push_back(o);
+        } else {
+            if (o.kind == Kind::Event) fail_unsupported("graph output '" + o.name + "': an event output is not supported beside a post-mix graph");
+            ps.post.outputs.push_back(o);
+        }
+    }
+    for (const GNode& n : g.nodes) {
+        GNode c = n;
+        c.bus = false;
+        (n.bus ? ps.post : ps.voice).nodes.push_back(c);
+    }
+    for (const GEdge& e : g.edges) {
+        const std::string dn = dst_node(e), d = trimmed(e.dst);
+        const bool to_bus = bus.count(dn) > 0, to_output = dn.empty() && outputs.count(d) && d != S;
+        bool reads_bus = false, reads_sum = count_node_refs(e.src, S) > 0;
+        std::string voice_node, bad_input;
+        for (const GNode& n : g.nodes) {
+            if (!count_node_refs(e.src, n.name)) continue;
+            if (n.bus) reads_bus = true;
+            else voice_node = n.name;
+        }
+        for (const auto& kv : inputs)
+            if (kv.first != S && count_node_refs(e.src, kv.first) && (kv.second->kind != Kind::Value || kv.second->per_voice)) bad_input = kv.first;
+        if (to_bus) {
+            if (!voice_node.empty())
+                fail_unsupported("node '" + voice_node + "' feeds both the voices and the post-mix node '" + dn + "' ('" + e.src + " -> " + e.dst +
+                                 "'): a node belongs to the voices or to the post-mix graph");
+            if (!bad_input.empty())
+                fail_unsupported("post-mix node '" + dn + "': " + (inputs[bad_input]->kind == Kind::Event ? "an event edge" : "a per-voice input") + " into a post-mix node is not supported ('" +
+                                 e.src + " -> " + e.dst + "'); the wrapper's broadcast value inputs may feed post-mix ports");
+            ps.post.edges.push_back(e);
+        } else if (to_output && (reads_bus || reads_sum)) {
+            if (!voice_node.empty())
+                fail_unsupported("graph output '" + d + "' mixes the voices' node '" + voice_node + "' with the post-mix graph ('" + e.src + "')");
+            ps.post.edges.push_back(e);
+        } else if (to_output) {
+            // a dry output beside the post-mix graph (`voices.out -> dry`): the voice sum itself
+            if (trimmed(e.src) != sum_src)
+                fail_unsupported("more than one voice output feeds the post-mix graph: graph output '" + d + "' is fed by '" + e.src + "', the post-mix graph by '" +
+                                 sum_src + "'");
+            GEdge x = e;
+            x.src = S;
+            x.policy.clear();
+            ps.post.edges.push_back(x);
+        } else {
+            if (reads_bus)
+                fail_unsupported("post-mix node output feeds back into the voices ('" + e.src + " -> " + e.dst + "'): the post-mix graph runs behind the voice sum");
+            ps.voice.edges.push_back(e);
+        }
+    }
+    return true;
+}
+
+namespace {
+std::unique_ptr<CompiledGraph> compile_one(const GraphDesc& g_in, bool rules_checked = false);
+std::unique_ptr<CompiledGraph> compile_post(const GraphDesc& gp);
+} // namespace
+
 std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
 {
-    const auto gen = lower(g_in, nullptr);
+    bool any_bus = false;
+    for (const GNode& n : g_in.nodes) any_bus = any_bus || n.bus || n.type.rfind("MidiVoiceHandler", 0) == 0;
+    PostSplit ps;
+    if (!any_bus) return compile_one(g_in);
+    check_reference_rules(g_in);
+    if (!split_post_mix(expand(g_in), ps)) return compile_one(g_in);
+    std::unique_ptr<CompiledGraph> cg = compile_one(ps.voice, true);
+    if (cg->lpv > 1) fail_unsupported("a post-mix graph behind array-valued voices (" + std::to_string(cg->lpv) + " lanes per voice) is not supported");
+    ps.post.inputs.back().channels = (int)cg->voice_channels;
+    cg->post = compile_post(ps.post);
+    CompiledGraph& p = *cg->post;
+    for (const InputInfo& in : p.inputs) p.post_input_of.push_back(in.decl.kind == Kind::Stream ? -1 : cg->find_input(in.decl.name));
+    for (const GNode& n : ps.post.nodes) p.post_nodes.push_back(n.name);
+    // the engine's bus is the post-mix graph's
+    cg->channels = p.channels;
+    cg->output_channels = p.output_channels;
+    cg->latency_samples += p.latency_samples;
+    return cg;
+}
+
+namespace {
+// The general pass first; the `_z` pass before the `_z2` set is computed (find_zero_folds reads out.zero_slots); the `_z2`
+// pass folds both sets.
+std::unique_ptr<CompiledGraph> compile_one(const GraphDesc& g_in, bool rules_checked)
+{
+    const auto gen = lower(g_in, nullptr, false, rules_checked);
     CompiledGraph& out = *gen->out;
     std::set<int> zset = find_zero_chain(*gen);
-    const std::string zbody = lower_variant(g_in, zset, out);
+    const std::string zbody = lower_variant(g_in, zset, out, false, rules_checked);
     if (zbody.empty()) {
         zset.clear();
         out.zero_slots.clear();
@@ -5687,7 +5931,7 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     //  slot must be free -- it carries the engine's A/B switch, OG_STAGE_SPEC_SLOT)
     const char* ssk = ogabi::experiment_knob("OGC_STAGE_SPEC");
     out.stage_spec = !(ssk && atoi(ssk) == 0) && out.n_slots < 160;
-    std::string z2body = lower_variant(g_in, z2.nodes.empty() ? z2.nodes : all, out, out.stage_spec);
+    std::string z2body = lower_variant(g_in, z2.nodes.empty() ? z2.nodes : all, out, out.stage_spec, rules_checked);
     out.stage_spec = out.stage_spec && z2body.find("og::StageC<") != std::string::npos;
     if (z2body.empty()) {
         z2.nodes.clear();
@@ -5698,5 +5942,72 @@ std::unique_ptr<CompiledGraph> compile(const GraphDesc& g_in)
     write_units(*gen, zset, zbody, z2.nodes, z2body);
     return std::move(gen->out);
 }
+
+// The post-mix graph's pass: the phases of lower() on the description split_post_mix() cut out, the post-mix kernel frame
+// instead of the voice kernels', a unit of its own (og_kp_<hash>_00 without, _10 with the ramp table).
+std::unique_ptr<CompiledGraph> compile_post(const GraphDesc& gp)
+{
+    auto gen = std::make_unique<Lowered>(gp);
+    CompiledGraph& out = *gen->out;
+    out.name = gen->g.name;
+    out.is_post = true;
+    Codegen& cg = gen->cg;
+    Lowering& lw = gen->lw;
+    lw.declare_inputs_outputs();
+    lw.declare_nodes();
+    lw.wire_edges(lw.infer_overwritten_edges());
+    lw.prune_dead_nodes();
+    lw.kahn_order();
+    lw.schedule_order();
+    lw.assign_rate_domains();
+    lw.plan_pipeline_stages();
+    lw.find_inner_event_sources();
+    lw.emit_nodes();
+    lw.form_graph_output();
+    lw.choose_unroll();
+    if (out.output_channels.empty()) fail("the post-mix graph feeds no stream output of the graph");
+    if (out.lpv > 1 || cg.N != 1 || !out.players.empty() || !out.arrays.empty() || cg.blk_slot0 >= 0 || out.n_event_inputs != 0)
+        fail_unsupported("the post-mix graph uses a node form that is not supported behind the voice sum (array-valued, oversampled, sample-playing or block-offset-reading nodes)");
+    out.max_pipeline = 1;
+    out.can_split = out.wide4 = false;
+    out.pm_slot0 = out.n_slots;
+    out.n_slots += 5;
+    if (out.n_slots > 160) fail("the post-mix graph needs more than 160 uniform slots");
+    BodyWriter bw(lw);
+    bw.write_post_kernel();
+    for (const auto& kv : cg.user_fns) gen->body += kv.second;
+    gen->body += bw.body.str();
+    out.hash = fnv1a(gen->body + "|post" + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) + "|rt" + OG_RT_DIGEST + "|pm" + OG_PM_DIGEST +
+                     (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()));
+    char hs[32];
+    snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
+    std::ostringstream desc, pre, os;
+    desc << "// The post-mix kernel (one wave, one voice: the nodes behind the voice sum): " << out.state.size() << " state words, " << out.n_slots
+         << " uniform slots (" << out.pm_slot0 << "..: input rows, destination, row stride), " << out.n_ramps << " ramped inputs, " << out.n_streams
+         << " channel(s) in, " << out.voice_channels << " out.\n// Node order: ";
+    if (out.node_order.empty()) out.node_order = out.schedule_order;
+    for (auto& nn : out.node_order) desc << nn << " ";
+    if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
+    pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "") << "#include \"og_post_mix.hip.h\"\n\n"
+        << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
+        << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
+        << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"
+        << "// the voice sum: rows " << out.n_ramps << ".. of the per-frame table are the channels of the post-mix input (og::post_in)\n"
+        << "#define ST(row) og::post_in<decltype(chk)::pre>(pm_in, (row) - " << out.n_ramps << ", f - pbase, io, f)\n\n";
+    const std::string ns = std::string("og_gen_") + hs;
+    write_unit_head(os, gen->g.name, desc.str(), pre.str(), ns, 1, gen->body);
+    for (const char* v : {"00", "10"})
+        os << "extern \"C\" __global__ __launch_bounds__(64) void og_kp_" << hs << "_" << v << "(OgBlockArgs A) { " << ns << "::post_block<" << (v[0] == '1' ? "true" : "false")
+           << ">(A); }\n";
+    // (the host simulator's loader looks kernels up under the voice kernels' names, ramps x taps: a post-mix launch has no taps)
+    os << "#ifdef OG_HOSTSIM\n";
+    for (const char* v : {"00", "10", "01", "11"})
+        os << "extern \"C\" __global__ __launch_bounds__(64) void og_k_" << hs << "_" << v << "(OgBlockArgs A) { " << ns << "::post_block<" << (v[0] == '1' ? "true" : "false")
+           << ">(A); }\n";
+    os << "#endif\n";
+    out.source = os.str();
+    return std::move(gen->out);
+}
+} // namespace
 
 } // namespace ogc

@@ -188,6 +188,15 @@ struct CompiledGraph {
     HostFn tremolo_rate, tremolo_depth;
     std::string bus_ir_name;                            // Convolver::with_ir(<name>()): the registered response ("": Convolver::new())
     std::shared_ptr<const std::vector<float>> bus_ir;   // ... its taps as registered when the graph was lowered (null: the empty convolver)
+    // post-mix GRAPH (any other set of wrapper-level nodes behind the voice sum): those nodes compiled as a second graph of one
+    // voice whose last stream input carries the voice sum, run by its own one-wave kernel (og_kp_<hash>_{00,10},
+    // og_post_mix.hip.h) between the bus reduce and the copies.  The voice graph is compiled as if they were not there.
+    std::unique_ptr<CompiledGraph> post;
+    // ... and, in `post` itself:
+    bool is_post = false;
+    int pm_slot0 = -1;                    // first of the five slots the ENGINE fills per launch: input rows (2), destination (2), row stride
+    std::vector<int> post_input_of;       // per input of `post`: the wrapper's input it mirrors (-1: the voice sum)
+    std::vector<std::string> post_nodes;  // the partition: names of the post-mix nodes, in declaration order
     std::vector<UniformProg> uprogs;
     std::vector<int> release_slots; // release length in samples (ADSR_R_N) of every outer-rate envelope: sizes the reciprocal table
     int n_slots = 0;
@@ -211,6 +220,16 @@ struct CompiledGraph {
                                              // per-frame dataflow, which is scheduled depth first from its sinks)
     int find_input(const std::string& n) const;
 };
+
+// The partition of an EXPANDED description whose bus nodes form a post-mix graph: `voice` is the description without them (its
+// one stream output is the voice sum), `post` holds them -- the wrapper's broadcast value inputs in order, then the stream
+// input `sum_input` (the voice sum; compile() sets its width), the graph's outputs but the sum.  False (nothing written): no
+// bus node, or a lone Tremolo / Convolver (their own stages).  Throws what compile() throws for the shapes it refuses.
+struct PostSplit {
+    GraphDesc voice, post;
+    std::string sum_input;
+};
+bool split_post_mix(const GraphDesc& expanded, PostSplit& out);
 
 // Throws std::runtime_error with a diagnostic on malformed/unsupported graphs.
 std::unique_ptr<CompiledGraph> compile(const GraphDesc& g);

@@ -7,6 +7,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -43,16 +46,17 @@ std::string slurp(const std::string& path)
 std::vector<char> compile_to_code(const ogc::CompiledGraph& cg, const char* arch)
 {
     const std::string dir = csrc_dir();
-    const char* names[7] = {"og_kernel_rt.hip.h", "og_nodes.hip.h", "og_math.h", "og_adsr_params.hip.h", "og_sample_player.hip.h", "og_stage_uniform.hip.h",
-                            "og_node_array.hip.h"};
-    std::string bodies[7];
-    const char* srcs[7];
-    for (int i = 0; i < 7; ++i) {
+    constexpr int NH = 8;
+    const char* names[NH] = {"og_kernel_rt.hip.h", "og_nodes.hip.h", "og_math.h", "og_adsr_params.hip.h", "og_sample_player.hip.h", "og_stage_uniform.hip.h",
+                             "og_node_array.hip.h", "og_post_mix.hip.h"};
+    std::string bodies[NH];
+    const char* srcs[NH];
+    for (int i = 0; i < NH; ++i) {
         bodies[i] = slurp(dir + "/" + names[i]);
         srcs[i] = bodies[i].c_str();
     }
     hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source + cg.zero2_source).c_str(), (cg.name + ".hip").c_str(), 7, srcs, names) != HIPRTC_SUCCESS)
+    if (hiprtcCreateProgram(&prog, (cg.source + cg.zero_source + cg.zero2_source).c_str(), (cg.name + ".hip").c_str(), NH, srcs, names) != HIPRTC_SUCCESS)
         throw std::runtime_error("oscen jit: hiprtcCreateProgram failed");
     std::string archopt = std::string("--offload-arch=") + arch;
     const char* opts[] = {archopt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-DOG_JIT=1"};
@@ -144,13 +148,37 @@ std::unique_ptr<OgJitKernel> og_jit_compile(const ogc::CompiledGraph& cg)
     std::string arch = prop.gcnArchName;
     size_t colon = arch.find(':');
     if (colon != std::string::npos) arch = arch.substr(0, colon);
-    std::vector<char> code = compile_to_code(cg, arch.c_str());
+    // The code object of a unit is kept for the life of the process, by kernel hash (it covers the unit's text and the device
+    // headers) and architecture: a second engine of the same graph -- a twin for an A/B, a snapshot's target, the next test of
+    // a suite -- loads the module again and does not wait for hiprtc.
+    static std::mutex cache_lock;
+    static std::map<std::pair<uint64_t, std::string>, std::shared_ptr<const std::vector<char>>> cache;
+    std::shared_ptr<const std::vector<char>> code;
+    {
+        std::lock_guard<std::mutex> g(cache_lock);
+        auto it = cache.find({cg.hash, arch});
+        if (it != cache.end()) code = it->second;
+    }
+    if (!code) {
+        code = std::make_shared<const std::vector<char>>(compile_to_code(cg, arch.c_str()));
+        std::lock_guard<std::mutex> g(cache_lock);
+        cache[{cg.hash, arch}] = code;
+    }
     std::unique_ptr<JitImpl> k(new JitImpl);
     k->lpv = (unsigned)cg.lpv;
-    if (hipModuleLoadData(&k->mod, code.data()) != hipSuccess) throw std::runtime_error("oscen jit: hipModuleLoadData failed");
+    if (hipModuleLoadData(&k->mod, code->data()) != hipSuccess) throw std::runtime_error("oscen jit: hipModuleLoadData failed");
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)cg.hash);
     const char* var[4] = {"00", "10", "01", "11"};
+    if (cg.is_post) { // a post-mix unit (og_graph.cpp, compile_post): og_kp_<hash>_00 / _10, one wave, no taps
+        for (int i = 0; i < 2; ++i) {
+            const std::string name = std::string("og_kp_") + hs + "_" + var[i];
+            if (hipModuleGetFunction(&k->fn[i], k->mod, name.c_str()) != hipSuccess)
+                throw std::runtime_error("oscen jit: kernel " + name + " not found in module");
+            k->fn[i + 2] = k->fn[i];
+        }
+        return k;
+    }
     for (int i = 0; i < 4; ++i) {
         std::string name = std::string("og_k_") + hs + "_" + var[i];
         if (hipModuleGetFunction(&k->fn[i], k->mod, name.c_str()) != hipSuccess)

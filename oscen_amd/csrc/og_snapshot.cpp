@@ -1,5 +1,6 @@
 // og_snapshot.cpp -- state snapshots of an engine behind the C ABI: og_state_bytes, og_save_state, og_load_state.
 #include "og_engine.h"
+#include "og_post_mix_host.h"
 
 // ---- state snapshot ---------------------------------------------------------------------------------------------
 // blob = DSP state (state planes, lane arrays, post-mix phase, delay lines) + control block: frame counter, the value
@@ -109,6 +110,18 @@ size_t control_bytes(const og_engine* e, size_t n_events, bool grouped)
            (grouped ? (size_t)e->V * sizeof(uint32_t) : 0);
 }
 size_t control_bytes(const og_engine* e, size_t n_events) { return control_bytes(e, n_events, !e->phys_of.empty()); }
+
+// Post-mix graph: a section of its own at the very END of the blob (og_post_mix_host.h), only in blobs of graphs that have
+// one -- the second state image and its delay lines
+ogpm::Layout post_layout(const og_engine* e)
+{
+    ogpm::Layout l;
+    if (!e->post_on()) return l;
+    for (const auto& w : e->cg->post->state) l.state_names.push_back(w.name);
+    for (size_t k = 0; k < e->cg->post->rings.size(); ++k) l.ring_caps.push_back(e->pm_ring_cap[k]);
+    return l;
+}
+size_t post_bytes(const og_engine* e) { return e->post_on() ? ogpm::section_bytes(post_layout(e)) : 0; }
 } // namespace
 
 extern "C" {
@@ -120,7 +133,7 @@ size_t og_state_bytes(const og_engine* e)
     if (!e) return 0;
     std::vector<SnapEvent> evs;
     collect_unconsumed(e, evs);
-    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e);
+    return dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e) + post_bytes(e);
     });
 }
 
@@ -132,7 +145,7 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
         e->flush_bus(); // queued blocks consume their events first: what is collected below is what frame_now has not reached
         std::vector<SnapEvent> evs;
         collect_unconsumed(e, evs);
-        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e)) throw std::runtime_error("buffer too small");
+        if (cap < dsp_bytes(e) + control_bytes(e, evs.size()) + conv_bytes(e) + samples_bytes(e) + post_bytes(e)) throw std::runtime_error("buffer too small");
         const size_t a = e->cg->state.size() * (size_t)e->V * 4, b = e->cg->lane_state.size() * (size_t)e->V * e->cg->lpv * e->cg->lane_width * 4;
         e->bounce.d2h(dst, e->d_state, a, e->stream);
         if (b) e->bounce.d2h((char*)dst + a, e->d_lane_state, b, e->stream);
@@ -203,6 +216,19 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
                 }
             }
         }
+        if (e->post_on()) {
+            const ogpm::Layout l = post_layout(e);
+            const ogpm::SectionHead ph = ogpm::make_head(l);
+            memcpy(p, &ph, sizeof ph);
+            if (!l.state_names.empty()) e->bounce.d2h(p + ogpm::words_offset(), e->d_pm_state, l.state_names.size() * 4, e->stream);
+            size_t at = ogpm::rings_offset(l);
+            for (size_t k = 0; k < l.ring_caps.size(); ++k) {
+                if (l.ring_caps[k]) e->bounce.d2h(p + at, e->d_pm_ring[k], (size_t)l.ring_caps[k] * 4, e->stream);
+                at += (size_t)l.ring_caps[k] * 4;
+            }
+            HIPCK(hipStreamSynchronize(e->stream));
+            p += at;
+        }
         return OG_OK;
     });
 }
@@ -210,6 +236,21 @@ int og_save_state(og_engine* e, void* dst, size_t cap)
 int og_load_state(og_engine* e, const void* src, size_t len)
 {
     if (!e || !src) return set_err(OG_E_INVALID, "null argument");
+    // the post-mix graph's section closes the blob: its head is checked before anything is believed, and everything below
+    // sees the blob without it
+    const size_t pm_bytes = post_bytes(e);
+    ogpm::Layout pm_layout;
+    if (pm_bytes) {
+        const int rc = ogabi::guard([&]() -> int {
+            pm_layout = post_layout(e);
+            const size_t at = len > pm_bytes ? len - pm_bytes : 0;
+            const std::string bad = ogpm::check(pm_layout, (const char*)src + at, len - at);
+            return bad.empty() ? OG_OK : set_err(OG_E_INVALID, bad);
+        });
+        if (rc != OG_OK) return rc;
+        len -= pm_bytes;
+    }
+    const char* const pm_src = (const char*)src + len;
     const size_t dsp = dsp_bytes(e);
     if (!e->cg->arrays.empty()) { // the node-array section names its fields: checked before anything else is believed
         const int rc = ogabi::guard([&]() -> int {
@@ -371,6 +412,14 @@ int og_load_state(og_engine* e, const void* src, size_t len)
             e->bounce.h2d(e->d_narr, (const char*)src + off, e->narr_bytes(), e->stream);
             e->narr_dirty = true;
             off += e->narr_bytes();
+        }
+        if (pm_bytes) {
+            if (!pm_layout.state_names.empty()) e->bounce.h2d(e->d_pm_state, pm_src + ogpm::words_offset(), pm_layout.state_names.size() * 4, e->stream);
+            size_t at = ogpm::rings_offset(pm_layout);
+            for (size_t k = 0; k < pm_layout.ring_caps.size(); ++k) {
+                if (pm_layout.ring_caps[k]) e->bounce.h2d(e->d_pm_ring[k], pm_src + at, (size_t)pm_layout.ring_caps[k] * 4, e->stream);
+                at += (size_t)pm_layout.ring_caps[k] * 4;
+            }
         }
         e->reset_timeline();
         HIPCK(hipStreamSynchronize(e->stream));
