@@ -174,6 +174,10 @@ extern "C" {
     pub fn og_node_array_info(e: *const og_engine, path: *const c_char, length: *mut u32, is_uint: *mut c_int) -> c_int;
     pub fn og_read_node_array(e: *mut og_engine, path: *const c_char, first_voice: u32, count: u32, out: *mut c_void) -> c_int;
     pub fn og_write_node_array(e: *mut og_engine, path: *const c_char, first_voice: u32, count: u32, data: *const c_void) -> c_int;
+    pub fn og_scope_info(e: *const og_engine, node_path: *const c_char, capacity: *mut u32, auto_detect: *mut c_int) -> c_int;
+    pub fn og_read_scope(e: *mut og_engine, node_path: *const c_char, first_voice: u32, n_voices: u32, sample_count: u32, samples: *mut c_float,
+                         n_samples: *mut u32, triggered: *mut c_float, n_triggered: *mut u32) -> c_int;
+    pub fn og_clear_scope_triggered(e: *mut og_engine, node_path: *const c_char, voices: *const u32, n: u32) -> c_int;
 }
 extern "C" {
     pub fn og_cluster_read_output_events(c: *mut og_cluster, buf: *mut og_out_event, cap: u32, n: *mut u32, n_overflowed: *mut u64) -> c_int;

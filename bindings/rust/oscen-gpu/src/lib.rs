@@ -362,6 +362,29 @@ impl<const IN: usize> GpuGraph<IN> {
         let c_path = CString::new(path).unwrap();
         ck(unsafe { sys::og_write_node_array(self.e, c_path.as_ptr(), first_voice, (rows.len() / length as usize) as u32, rows.as_ptr().cast()) }).map(|_| ())
     }
+    /// (capacity, auto_detect) of an Oscilloscope node: "scope", "scopes[k]", "nested.scope"
+    pub fn scope_info(&self, node_path: &str) -> Result<(u32, bool), GpuError> {
+        let c_path = CString::new(node_path).unwrap();
+        let (mut capacity, mut auto_detect) = (0u32, 0i32);
+        ck(unsafe { sys::og_scope_info(self.e, c_path.as_ptr(), &mut capacity, &mut auto_detect) })?;
+        Ok((capacity, auto_detect != 0))
+    }
+    /// `OscilloscopeHandle::snapshot(sample_count)` of voices `first_voice .. first_voice + n_voices`: per voice (samples, triggered)
+    pub fn read_scope(&mut self, node_path: &str, first_voice: u32, n_voices: u32, sample_count: u32) -> Result<Vec<(Vec<f32>, Vec<f32>)>, GpuError> {
+        let (capacity, _) = self.scope_info(node_path)?;
+        let c_path = CString::new(node_path).unwrap();
+        let (row, cap, n) = (sample_count.max(1) as usize, capacity as usize, n_voices as usize);
+        let (mut s, mut t) = (vec![0.0f32; n * row], vec![0.0f32; n * cap]);
+        let (mut ns, mut nt) = (vec![0u32; n], vec![0u32; n]);
+        ck(unsafe { sys::og_read_scope(self.e, c_path.as_ptr(), first_voice, n_voices, sample_count, s.as_mut_ptr(), ns.as_mut_ptr(), t.as_mut_ptr(), nt.as_mut_ptr()) })?;
+        Ok((0..n).map(|v| (s[v * row..v * row + ns[v] as usize].to_vec(), t[v * cap..v * cap + nt[v] as usize].to_vec())).collect())
+    }
+    /// `clear_triggered()` of the listed voices (None: all), behind the blocks already queued
+    pub fn clear_scope_triggered(&mut self, node_path: &str, voices: Option<&[u32]>) -> Result<(), GpuError> {
+        let c_path = CString::new(node_path).unwrap();
+        let (p, n) = voices.map_or((std::ptr::null(), 0u32), |v| (v.as_ptr(), v.len() as u32));
+        ck(unsafe { sys::og_clear_scope_triggered(self.e, c_path.as_ptr(), p, n) }).map(|_| ())
+    }
     /// the events the voices pushed into the graph's event outputs since the last call, ordered by (frame, voice, push
     /// order) -- what iterating `graph.<event_output>` gives after process_block -- and how many the log could not hold
     pub fn read_output_events(&mut self, cap: usize) -> Result<(Vec<sys::og_out_event>, u64), GpuError> {

@@ -459,6 +459,26 @@ int og_read_state_field(og_engine* e, const char* path, uint32_t first_voice, ui
 int og_node_array_info(const og_engine* e, const char* path, uint32_t* length, int* is_uint);
 int og_read_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, void* out);
 int og_write_node_array(og_engine* e, const char* path, uint32_t first_voice, uint32_t count, const void* data);
+/* Oscilloscope nodes (`scope = Oscilloscope::new(256)`, ::with_handle, ::with_auto_detect: oscen-lib/src/oscilloscope/mod.rs).
+ * The node passes its input through, keeps the last `capacity` samples of every voice and freezes the last period on a rising
+ * zero crossing; these calls are what the reference's OscilloscopeHandle is to a UI thread.  node_path = "<node>",
+ * "<array>[k]" for an element of a node array, "nested.node" inside a nested graph type.
+ * og_scope_info: the capacity (after the reference's max(1)) and whether the node detects the period itself.
+ * og_read_scope: snapshot(sample_count) of voices first_voice .. -- samples[v][0 .. n_samples[v]) in rows of max(sample_count, 1)
+ *   floats: the last clamp(sample_count, 1, min(written, capacity)) samples in time order; triggered[v][0 .. n_triggered[v]) in
+ *   rows of `capacity` floats: the window the last crossing froze (length 0: none, or cleared).  Both are empty for a voice
+ *   nothing was pushed to.  Either pair of pointers may be NULL.  Queued blocks are launched first and the device is waited
+ *   for; a read moves the node's whole planes, so read rarely on a large bank.
+ * og_clear_scope_triggered: clear_triggered() for the n listed voices (voices == NULL: all) -- behind the queued blocks, on a
+ *   launch boundary; the next crossing fills the window again.
+ * The state words written, triggered_length, last_sample, detected_period and copies (windows this voice copied out of its
+ * ring since og_init: a diagnostic that depends on where launches are cut) are read with og_read_state_field("<node>.<word>").
+ * Voices are the caller's numbers (og_group_voices).  OG_E_INVALID: null arguments, an unknown path or a node that is no
+ * Oscilloscope, a voice past the bank. */
+int og_scope_info(const og_engine* e, const char* node_path, uint32_t* capacity, int* auto_detect);
+int og_read_scope(og_engine* e, const char* node_path, uint32_t first_voice, uint32_t n_voices, uint32_t sample_count, float* samples,
+                  uint32_t* n_samples, float* triggered, uint32_t* n_triggered);
+int og_clear_scope_triggered(og_engine* e, const char* node_path, const uint32_t* voices, uint32_t n);
 
 /* Introspection of `graph.voices[i].<out>` (tests poke node fields in the
  * reference): record the per-voice output of the listed voices during the

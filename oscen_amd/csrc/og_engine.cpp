@@ -2307,6 +2307,94 @@ int og_write_node_array(og_engine* e, const char* path, uint32_t first_voice, ui
     return node_array_transfer(e, path, first_voice, count, nullptr, data);
 }
 
+// ---- Oscilloscope nodes (og_scope.hip.h; what a read reconstructs: og_scope_host.h) -----------------------------------------
+static int find_scope(const og_engine* e, const char* path)
+{
+    const std::string p = ogscope::flat_node(path);
+    for (size_t k = 0; k < e->cg->scopes.size(); ++k)
+        if (e->cg->scopes[k].name == p) return (int)k;
+    return -1;
+}
+int og_scope_info(const og_engine* e, const char* node_path, uint32_t* capacity, int* auto_detect)
+{
+    if (!e || !node_path) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        const int k = find_scope(e, node_path);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no Oscilloscope named '") + node_path + "'");
+        if (capacity) *capacity = e->cg->scopes[k].capacity;
+        if (auto_detect) *auto_detect = e->cg->scopes[k].auto_detect ? 1 : 0;
+        return OG_OK;
+    });
+}
+int og_read_scope(og_engine* e, const char* node_path, uint32_t first_voice, uint32_t n_voices, uint32_t sample_count, float* samples, uint32_t* n_samples,
+                  float* triggered, uint32_t* n_triggered)
+{
+    if (!e || !node_path) return set_err(OG_E_INVALID, "null argument");
+    if ((samples && !n_samples) || (triggered && !n_triggered)) return set_err(OG_E_INVALID, "og_read_scope: rows without their lengths");
+    return guard([&]() -> int {
+        const int k = find_scope(e, node_path);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no Oscilloscope named '") + node_path + "'");
+        if ((uint64_t)first_voice + n_voices > e->V) return set_err(OG_E_INVALID, "voice range out of bounds");
+        HIPCK(hipSetDevice(e->device));
+        e->flush_bus();
+        if (!n_voices) return OG_OK;
+        const auto& sp = e->cg->scopes[k];
+        const auto& fr = e->cg->arrays[sp.ring_array];
+        const auto& ff = e->cg->arrays[sp.frozen_array];
+        const uint32_t V = e->V;
+        // whole planes, as og_read_node_array: the planes of a field are contiguous, the columns of a voice range are not
+        std::vector<float> ring((size_t)fr.length * V), frozen((size_t)ff.length * V);
+        const int words[5] = {sp.w_write_pos, sp.w_written, sp.w_triggered_length, sp.w_window_end, sp.w_pending};
+        std::vector<uint32_t> planes((size_t)5 * V);
+        e->bounce.d2h(ring.data(), e->d_narr + (size_t)fr.base * V, ring.size() * 4, e->stream);
+        e->bounce.d2h(frozen.data(), e->d_narr + (size_t)ff.base * V, frozen.size() * 4, e->stream);
+        for (int w = 0; w < 5; ++w) e->bounce.d2h(planes.data() + (size_t)w * V, e->d_state + (size_t)words[w] * V, (size_t)V * 4, e->stream);
+        HIPCK(hipStreamSynchronize(e->stream));
+        const uint32_t row = sample_count < 1u ? 1u : sample_count; // (snapshot() hands out at least one sample)
+        for (uint32_t i = 0; i < n_voices; ++i) {
+            const uint32_t s = e->phys(first_voice + i);
+            ogscope::Words w;
+            w.write_pos = planes[s];
+            w.written = planes[(size_t)V + s];
+            w.triggered_length = planes[(size_t)2 * V + s];
+            w.window_end = planes[(size_t)3 * V + s];
+            w.pending = planes[(size_t)4 * V + s];
+            ogscope::snapshot(sp.capacity, ogscope::Column{ring.data() + s, V}, ogscope::Column{frozen.data() + s, V}, w, sample_count,
+                              samples ? samples + (size_t)i * row : nullptr, n_samples ? n_samples + i : nullptr,
+                              triggered ? triggered + (size_t)i * sp.capacity : nullptr, n_triggered ? n_triggered + i : nullptr);
+        }
+        return OG_OK;
+    });
+}
+int og_clear_scope_triggered(og_engine* e, const char* node_path, const uint32_t* voices, uint32_t n)
+{
+    if (!e || !node_path) return set_err(OG_E_INVALID, "null argument");
+    return guard([&]() -> int {
+        const int k = find_scope(e, node_path);
+        if (k < 0) return set_err(OG_E_INVALID, std::string("no Oscilloscope named '") + node_path + "'");
+        for (uint32_t i = 0; voices && i < n; ++i)
+            if (voices[i] >= e->V) return set_err(OG_E_INVALID, "voice " + std::to_string(voices[i]) + " out of bounds");
+        HIPCK(hipSetDevice(e->device));
+        e->flush_bus(); // queued blocks keep what they were queued under: the clear lands behind them, on a launch boundary
+        const auto& sp = e->cg->scopes[k];
+        // clear_triggered() (mod.rs:125-127): triggered_length = 0 -- and a window still pending in the ring is dropped with it
+        for (const int w : {sp.w_triggered_length, sp.w_pending}) {
+            uint32_t* d = e->d_state + (size_t)w * e->V;
+            if (!voices) {
+                HIPCK(hipMemsetAsync(d, 0, (size_t)e->V * 4, e->stream));
+            } else if (n) {
+                std::vector<uint32_t> plane(e->V);
+                e->bounce.d2h(plane.data(), d, (size_t)e->V * 4, e->stream);
+                HIPCK(hipStreamSynchronize(e->stream));
+                for (uint32_t i = 0; i < n; ++i) plane[e->phys(voices[i])] = 0u;
+                e->bounce.h2d(d, plane.data(), (size_t)e->V * 4, e->stream);
+            }
+        }
+        HIPCK(hipStreamSynchronize(e->stream));
+        return OG_OK;
+    });
+}
+
 int og_set_voice_taps(og_engine* e, const uint32_t* voices, uint32_t n)
 {
     if (!e || (n && !voices)) return set_err(OG_E_INVALID, "null argument");

@@ -26,6 +26,7 @@
 #include "og_graph.h"
 #include "og_jit.h"
 #include "og_node_array_host.h"
+#include "og_scope_host.h"
 #include "og_registry.h"
 #include "og_timeline.h"
 

@@ -1,6 +1,7 @@
 // og_graph.cpp -- graph lowering + HIP code generation (see og_graph.h).
 #include "og_graph.h"
 #include "og_rt_digest.h" // OG_RT_DIGEST: digest of the device headers the generated kernels include
+#include "og_scope_host.h"
 
 #include <algorithm>
 #include <cctype>
@@ -38,6 +39,7 @@ namespace {
 [[noreturn]] void fail(const std::string& m) { throw std::runtime_error("oscen graph: " + m); }
 // a well-formed graph that uses something this build lacks: carries OG_E_UNSUPPORTED (og_abi.h)
 [[noreturn]] void fail_unsupported(const std::string& m) { throw ogabi::Unsupported("oscen graph: " + m); }
+bool is_scope(const std::string& type); // an Oscilloscope (emit_scope)
 
 std::string flit(float v)
 { // exact float literal
@@ -779,6 +781,9 @@ struct Codegen {
             v.inner = nodes[ni].domain == 1; // last tick's value, at the producer's rate
             return v;
         }
+        if (vit == node_outputs.end() && port == "handle" && nodes[ni].decl && is_scope(nodes[ni].decl->type))
+            fail_unsupported("node '" + node_name + "': the `handle` output of an Oscilloscope cannot be connected in this version -- the scope is read "
+                             "with og_read_scope");
         if (vit == node_outputs.end())
             fail("node '" + node_name + "' has no output '" + port + "' (or it is read before it runs)");
         Val v = vit->second;
@@ -1641,6 +1646,91 @@ void emit_sample_player(NodeCtx& x)
 }
 bool is_sample_player(const std::string& type) { return normalize_type(type).rfind("SamplePlayer", 0) == 0; }
 
+// the node-array pool (og_node_array.hip.h): its address reaches the kernel in two slots the engine fills per launch
+void use_node_array_pool(NodeCtx& x)
+{
+    if (x.cg.out.narr_slot0 >= 0) return;
+    x.cg.out.narr_slot0 = x.cg.new_slot([](const UEnv&) { return 0u; });
+    (void)x.cg.new_slot([](const UEnv&) { return 0u; });
+    x.cg.common_decl << "    og::narr_word* const narr_pool = og::node_array_pool(A, " << x.cg.out.narr_slot0 << ");\n";
+}
+
+// Oscilloscope (oscen-lib/src/oscilloscope/mod.rs): pass-through, a ring of the last `capacity` samples, a window frozen on a
+// rising zero crossing.  The ring and the window are planes of the node-array pool, the rest is state words (og_scope.hip.h)
+bool is_scope(const std::string& type) { return normalize_type(type).rfind("Oscilloscope::", 0) == 0; }
+// new(capacity) (mod.rs:180), with_handle / with_auto_detect(OscilloscopeHandle::new(capacity)) (195, 210; the builder API
+// passes the capacity itself): capacity.max(1) (mod.rs:21)
+uint32_t scope_capacity(const GNode& n)
+{
+    const std::string raw = n.raw_args.empty() ? std::string() : n.raw_args[0];
+    long long cap = -1;
+    if (!raw.empty()) {
+        if (n.type == "Oscilloscope::new") fail("node '" + n.name + "': constructor argument '" + raw + "' of " + n.type + " is not a number");
+        cap = ogscope::handle_capacity(raw);
+        if (cap < 0)
+            fail_unsupported("node '" + n.name + "': an Oscilloscope takes its handle as `OscilloscopeHandle::new(<integer literal>)`; the handle '" + raw +
+                             "' is not supported in this version (the scope is read with og_read_scope, not through a shared handle)");
+    } else {
+        const float a = n.args.empty() ? -1.0f : n.args[0];
+        if (!(a >= 0.0f) || a != floorf(a) || a > 1.0e9f) fail("node '" + n.name + "': the capacity of an Oscilloscope is a non-negative integer");
+        cap = (long long)a;
+    }
+    if (cap < 1) cap = 1;
+    if (cap > (long long)ogscope::MAX_CAPACITY)
+        fail_unsupported("node '" + n.name + "': an Oscilloscope of " + std::to_string(cap) + " samples is not supported, at most " +
+                         std::to_string(ogscope::MAX_CAPACITY) + " are (the node-array field limit)");
+    return (uint32_t)cap;
+}
+void emit_scope(NodeCtx& x)
+{
+    const std::string nm = x.n.decl->name;
+    const bool auto_detect = x.n.type->variant == 1;
+    if (x.cg.out.lpv > 1)
+        fail_unsupported("node '" + nm + "': an Oscilloscope inside an array-valued voice ([f32; 32] nodes) is not supported in this version");
+    if (x.n.domain == 1 || x.n.decl->rate_factor != 1)
+        fail_unsupported("node '" + nm + "': an Oscilloscope in an oversampled (`* N`) domain is not supported in this version");
+    const uint32_t cap = scope_capacity(*x.n.decl), P = ogscope::ring_len(cap);
+    const Val in = x.in("input");
+    // trigger_period defaults to `capacity as f32` (mod.rs:186, 201, 216); with the handle spelt out the argument is no number
+    const Val tp = x.connected("trigger_period") ? x.in("trigger_period") : vconst((float)cap);
+    const Val te = x.in("trigger_enabled");
+    use_node_array_pool(x);
+    const uint32_t ring_base = x.cg.out.array_words(), frozen_base = ring_base + P;
+    if ((uint64_t)frozen_base + cap > NODE_ARRAY_WORDS_MAX)
+        fail_unsupported("node '" + nm + "' (Oscilloscope): the array fields of this graph take more than " + std::to_string(NODE_ARRAY_WORDS_MAX) + " words per voice");
+    CompiledGraph::ScopeSpec sp;
+    sp.name = nm;
+    sp.capacity = cap;
+    sp.auto_detect = auto_detect;
+    sp.ring_array = (int)x.cg.out.arrays.size();
+    x.cg.out.arrays.push_back({nm + ".ring", ring_base, P, false, 0u});
+    sp.frozen_array = (int)x.cg.out.arrays.size();
+    x.cg.out.arrays.push_back({nm + ".triggered", frozen_base, cap, false, 0u});
+    auto word = [&]() { return (int)x.cg.out.state.size() - 1; };
+    const std::string wp = x.state_u("write_pos", 0);
+    sp.w_write_pos = word();
+    const std::string wr = x.state_u("written", 0);
+    sp.w_written = word();
+    const std::string ls = x.state_f("last_sample", [](const UEnv&) { return 0.0f; });
+    const std::string psc = x.state_u("period_sample_count", 0);
+    const std::string dp = x.state_u("detected_period", cap); // mod.rs:191
+    const std::string tl = x.state_u("triggered_length", 0);
+    sp.w_triggered_length = word();
+    const std::string we = x.state_u("window_end", 0);
+    sp.w_window_end = word();
+    const std::string pd = x.state_u("pending", 0);
+    sp.w_pending = word();
+    const std::string cp = x.state_u("copies", 0);
+    x.cg.out.scopes.push_back(sp);
+    const std::string S = x.p + "sc", T = std::to_string(cap) + "u";
+    x.cg.S().decl << "    og::Scope<" << T << "> " << S << ";\n";
+    x.cg.S().pre << "    " << S << " = og::scope_begin<" << T << ">(narr_pool, " << ring_base << "u, " << frozen_base << "u, A.n_voices, c.v, c.valid, " << wp << ", "
+                 << we << ", " << tl << ");\n";
+    x.cg.S().chunk_begin << "        og::scope_chunk_begin<" << T << ">(" << S << ", " << wp << ", " << we << ", " << tl << ", " << pd << ", " << cp << ");\n";
+    x.set_out("output", std::string("og::scope_tick<") + (auto_detect ? "true" : "false") + ", " + T + ">(" + S + ", " + in.e + ", " + tp.e + ", " + te.e + ", " + wp +
+                            ", " + wr + ", " + ls + ", " + psc + ", " + dp + ", " + tl + ", " + we + ", " + pd + ")");
+}
+
 // (inputs are resolved in separate statements: operand evaluation order is unspecified in C++ and
 //  resolving an input can allocate cut-crossing channels, whose numbering must be deterministic)
 void emit_binary(NodeCtx& x, const char* a, const char* b, const char* op)
@@ -1853,6 +1943,10 @@ const std::map<std::string, NodeTypeInfo>& registry()
             t.out_channels = {w};
             r["SamplePlayer<" + std::to_string(w) + ">::new"] = t;
         }
+        // the capacity is the one argument of all three; the text front end also takes `OscilloscopeHandle::new(<literal>)` there
+        for (const char* ctor : {"new", "with_handle", "with_auto_detect"})
+            r[std::string("Oscilloscope::") + ctor] = {{{"input", S, 0, -1}, {"trigger_period", V, 0, 0}, {"trigger_enabled", V, 1.0f, -1}},
+                                                       {"output"}, emit_scope, std::string(ctor) == "with_auto_detect" ? 1 : 0, 1};
         r["AmplitudeSource::new"] = {{{"frequency", V, 440.0f, -1}, {"gate", E, 0, -1}, {"brightness", V, 30.0f, -1},
                                       {"velocity_scaling", V, 50.0f, -1}, {"decay_rate", V, 90.0f, -1},
                                       {"harmonic_decay", V, 70.0f, -1}, {"key_scaling", V, 50.0f, -1},
@@ -1935,11 +2029,7 @@ void emit_user(NodeCtx& x)
     for (const UserArray& a : u.arrays) {
         if (x.cg.out.lpv > 1)
             fail_unsupported("node '" + x.n.decl->name + "' (" + u.type + "): a node with array fields inside an array-valued voice ([f32; 32] nodes) is not supported in this version");
-        if (x.cg.out.narr_slot0 < 0) { // filled by the engine per launch: the pool's address
-            x.cg.out.narr_slot0 = x.cg.new_slot([](const UEnv&) { return 0u; });
-            (void)x.cg.new_slot([](const UEnv&) { return 0u; });
-            x.cg.common_decl << "    og::narr_word* const narr_pool = og::node_array_pool(A, " << x.cg.out.narr_slot0 << ");\n";
-        }
+        use_node_array_pool(x); // filled by the engine per launch: the pool's address
         const uint32_t base = x.cg.out.array_words();
         if ((uint64_t)base + a.length > NODE_ARRAY_WORDS_MAX)
             fail_unsupported("node '" + x.n.decl->name + "' (" + u.type + "): the array fields of this graph take more than " +
@@ -3502,7 +3592,7 @@ void Lowering::declare_nodes()
         if (convolver && !nd.bus)
             fail_unsupported("node '" + nd.name + "': a Convolver is only available as the post-mix (bus) node, fed by the summed voices -- not inside a "
                              "voice graph, oversampled or in a feedback path");
-        for (size_t a = 0; a < nd.raw_args.size() && !convolver; ++a)
+        for (size_t a = 0; a < nd.raw_args.size() && !convolver && !is_scope(nd.type); ++a) // (a scope's handle: scope_capacity)
             if (!nd.raw_args[a].empty())
                 fail("node '" + nd.name + "': constructor argument '" + nd.raw_args[a] + "' of " + nd.type + " is not a number");
         if (nd.args.size() != nti->nargs)
@@ -3996,6 +4086,7 @@ void Lowering::plan_pipeline_stages()
     for (int ni : order) any_delay = any_delay || is_sample_player(cg.nodes[ni].decl->type); // (sample frames: staged the same way)
     // (array fields of registered node types: one wave stays the sole owner of its voices' planes, og_node_array.hip.h)
     for (int ni : order) any_delay = any_delay || (cg.nodes[ni].type && cg.nodes[ni].type->user && !cg.nodes[ni].type->user->arrays.empty());
+    for (int ni : order) any_delay = any_delay || is_scope(cg.nodes[ni].decl->type); // (the same holds for a scope's ring, og_scope.hip.h)
     bool want = cg.N == 1 && out.lpv == 1 && order.size() >= 2 && !any_feedback && !cg.dynamic_events &&
                 !any_delay; // (round 4: several bus channels -- Frame<N> / several stream outputs -- run in the pipelines too)
     // estimated per-tick VALU cost of every node, in emission order
@@ -5610,7 +5701,8 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     out.hash = fnv1a(gen.body + "|lpv" + std::to_string(out.lpv) + (cg.ev_capacity != 2 ? "|evq" + std::to_string(cg.ev_capacity) : std::string()) +
                      "|wide" + wide_args + "|rt" + OG_RT_DIGEST + (cg.uses_adsrp ? std::string("|adsrp") + OG_ADSRP_DIGEST : std::string()) +
                      (out.players.empty() ? std::string() : std::string("|smp") + OG_SMP_DIGEST) +
-                     (out.arrays.empty() ? std::string() : std::string("|narr") + OG_NARR_DIGEST));
+                     (out.arrays.empty() ? std::string() : std::string("|narr") + OG_NARR_DIGEST) +
+                     (out.scopes.empty() ? std::string() : std::string("|scope") + OG_SCOPE_DIGEST));
     char hs[32];
     snprintf(hs, sizeof hs, "%016llx", (unsigned long long)out.hash);
 
@@ -5662,7 +5754,7 @@ void write_units(Lowered& gen, const std::set<int>& zset, const std::string& zbo
     if (cg.ev_capacity != 2) pre << "\n#define OG_NODE_EVENTS_PER_FRAME " << cg.ev_capacity << " // event_queue_capacity of a node type of this graph";
     pre << "\n#include \"og_kernel_rt.hip.h\"\n#include \"og_nodes.hip.h\"\n" << (cg.uses_adsrp ? "#include \"og_adsr_params.hip.h\"\n" : "")
         << (out.players.empty() ? "" : "#include \"og_sample_player.hip.h\"\n")
-        << (out.arrays.empty() ? "" : "#include \"og_node_array.hip.h\"\n") << "\n"
+        << (out.arrays.empty() ? "" : "#include \"og_node_array.hip.h\"\n") << (out.scopes.empty() ? "" : "#include \"og_scope.hip.h\"\n") << "\n"
         << "#if OG_NODE_EVENTS_PER_FRAME <= 4\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll\")\n#else\n#define OG_EV_LOOP_PRAGMA _Pragma(\"unroll 1\")\n#endif\n"
         << "#define SF(i) og::slot_f(A, (i))\n#define SU(i) og::slot_u(A, (i))\n"
         << "#define RV(row, slot) (RAMPS ? A.ramp_table[(size_t)(row) * A.ramp_stride + f] : og::slot_f(A, (slot)))\n"
@@ -5786,6 +5878,8 @@ bool split_post_mix(const GraphDesc& g, PostSplit& ps)
         if (!nti) fail("unknown node type '" + n.type + "' (node '" + n.name + "'); custom nodes are added with og_register_node");
         if (n.rate_factor != 1) fail_unsupported("post-mix node '" + n.name + "': an oversampled (* " + std::to_string(n.rate_factor) + ") node is not supported in a post-mix graph");
         if (n.type.rfind("SamplePlayer", 0) == 0) fail_unsupported("post-mix node '" + n.name + "': a SamplePlayer is not supported in a post-mix graph");
+        if (is_scope(n.type))
+            fail_unsupported("post-mix node '" + n.name + "': an Oscilloscope is not supported in a post-mix graph (the host receives the bus itself)");
         if (nti->lpv > 1 || (nti->user && !nti->user->arrays.empty()))
             fail_unsupported("post-mix node '" + n.name + "': a node type with array fields (" + n.type + ") is not supported in a post-mix graph");
         if (!nti->emit) fail_unsupported("post-mix node '" + n.name + "': node type '" + n.type + "' has no device body");

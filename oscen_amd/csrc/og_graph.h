@@ -167,6 +167,16 @@ struct CompiledGraph {
     std::vector<ArraySpec> arrays;
     int narr_slot0 = -1;
     uint32_t array_words() const { return arrays.empty() ? 0u : arrays.back().base + arrays.back().length; } // per voice
+    // Oscilloscope nodes (og_scope.hip.h): the physical ring and the frozen window are two entries of `arrays`
+    // ("<node>.ring", "<node>.triggered"), everything else is ordinary state words
+    struct ScopeSpec {
+        std::string name; // node name of the flattened graph
+        uint32_t capacity = 1;
+        bool auto_detect = false;
+        int ring_array = -1, frozen_array = -1; // indices into `arrays`
+        int w_write_pos = -1, w_written = -1, w_triggered_length = -1, w_window_end = -1, w_pending = -1; // state planes
+    };
+    std::vector<ScopeSpec> scopes;
     bool reads_block_starts = false;   // an event handler reads frame_offset: a launch carries the starts of its (at most 32) blocks
     int lpv = 1;                       // lanes per voice (8 for the electric-piano voice)
     int lane_width = 1;                // words a lane owns of every lane_state array (OG_HPL = 4 when lpv > 1)

@@ -46,9 +46,9 @@ std::string slurp(const std::string& path)
 std::vector<char> compile_to_code(const ogc::CompiledGraph& cg, const char* arch)
 {
     const std::string dir = csrc_dir();
-    constexpr int NH = 8;
+    constexpr int NH = 9;
     const char* names[NH] = {"og_kernel_rt.hip.h", "og_nodes.hip.h", "og_math.h", "og_adsr_params.hip.h", "og_sample_player.hip.h", "og_stage_uniform.hip.h",
-                             "og_node_array.hip.h", "og_post_mix.hip.h"};
+                             "og_node_array.hip.h", "og_post_mix.hip.h", "og_scope.hip.h"};
     std::string bodies[NH];
     const char* srcs[NH];
     for (int i = 0; i < NH; ++i) {
